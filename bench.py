@@ -1,13 +1,20 @@
 """Throughput benchmark of the DAF VGG16 Cityscapes->Foggy training step on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
 
 One step = one DAF iteration on one source + one target image (600x1200, synthetic,
 resident in HBM) per GPU: forward, loss, backward (+ RCCL gradient all-reduce for N>1),
 clip_gradient(10), SGD.  value = source images/s over the whole job (max-over-ranks
-step time).  Rank 0 prints one JSON line; see DESIGN.md §Measurement for the roofline
-and cpu_baseline fields.
+step time).  Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (roofline and
+cpu_baseline are null).  --full adds the per-launch conv / GEMM roofline (one untimed
+launch-counting step before the timed region, HIP events on its last step, the committed
+PMC traffic) and the CPU baseline of the oracle step; see DESIGN.md §Measurement for
+those fields.  --dump-outputs DIR writes what the last timed step handed back (its loss,
+the losses of all timed steps, a fixed sample of every updated parameter) as
+DIR/<name>.npy; the inputs depend on the arguments only, so two builds compare file by file.
 """
 import argparse
 import json
@@ -41,8 +48,15 @@ def parse():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--height", type=int, default=600)
     ap.add_argument("--width", type=int, default=1200)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the conv / GEMM roofline (per-launch events) and the "
+                         "CPU baseline; a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy "
+                         "(float32 / float64)")
     ap.add_argument("--cpu-baseline-steps", type=int, default=5,
-                    help="oracle CPU steps timed on rank 0 at N=1, after 2 untimed (0 disables)")
+                    help="--full: oracle CPU steps timed on rank 0 at N=1, after 2 untimed "
+                         "(0 disables)")
     ap.add_argument("--cpu-threads", type=int, default=16,
                     help="torch CPU threads of the baseline (the box's share of one GPU is 16)")
     ap.add_argument("--bucket-mb", type=float, default=32.0)
@@ -161,6 +175,81 @@ def cpu_baseline(steps, H, W, threads):
                       f"fp32 conv/linear, {threads} threads; median s/step = {t:.2f}"}
 
 
+def roofline_entry(a, records, n_prof):
+    """The result line's roofline field (--full): the dominant kernel family of the timed
+    conv + GEMM launches in ``records``, next to the committed PMC traffic."""
+    achieved, detail, conv_ms, conv_f, n_launch, dom, fams = conv_roofline(records)
+    if dom is None:  # TLOD_BENCH_NOPROF: no launch records
+        dom = {"family": "none", "math": "bf16x6", "achieved": 0.0, "peak": 1.0, "ms": 0.0,
+               "launches": 1, "bytes": 0.0}
+    traffic, traffic_src = measured_traffic(a)
+    fam_kernels = {"conv3x3/bf16x6": ("conv_fwd_bs_kernel", "conv_fwd_bs_ws_kernel",
+                                      "wgrad_ws_kernel"),
+                   "conv3x3/f32": ("conv_fwd_kernel", "conv_wgrad_kernel"),
+                   "conv1x1/bf16x6": ("conv_gemm_bs_kernel", "conv_wgrad_bs_kernel"),
+                   "gemm/bf16x6": ("gemm_bs_kernel",)}
+    dom_kernels = fam_kernels.get(dom["family"], ())
+    per_launch_pmc = None
+    if traffic and dom_kernels:
+        by_k = traffic["bytes_per_step_by_kernel"]
+        # a PMC pass that predates a kernel of the family cannot price this run's launches
+        if all(k in by_k for k in dom_kernels if k != "conv_fwd_bs_kernel"):
+            per_launch_pmc = round(sum(by_k.get(k, 0) for k in dom_kernels) /
+                                   (dom["launches"] / n_prof))
+    return {"bound": "mfma", "achieved": round(dom["achieved"], 2),
+            "peak": round(dom["peak"], 1), "unit": "TFLOP/s",
+            "frac": round(dom["achieved"] / dom["peak"], 4),
+            "traffic": per_launch_pmc,
+            "algorithmic_bytes": round(dom["bytes"] / dom["launches"]),
+            "traffic_source": traffic_src,
+            "traffic_note": "PMC HBM bytes per launch of the dominant kernels "
+                            f"({' + '.join(dom_kernels)}; FETCH_SIZE x2 + WRITE_SIZE) "
+                            "vs algorithmic bytes per launch (operands read once, "
+                            "result written once)" +
+                            ("" if per_launch_pmc is not None or not traffic else
+                             "; null: the committed PMC pass predates a kernel "
+                             "of the family"),
+            "traffic_by_kernel_per_step": (traffic or {}).get("bytes_per_step_by_kernel"),
+            "kernel": f"tlod {dom['family']} (the family with the most time of "
+                      "the timed conv + GEMM launches)",
+            "kernel_ms_per_step": round(dom["ms"] / n_prof, 3),
+            "profiled_steps": n_prof,
+            "families": fams,
+            "peak_basis": "f32-equivalent: algorithmic f32 FLOPs at the MFMA peak; "
+                          "bf16xN = 2516.6 TF bf16 dense / N products",
+            "all_conv_gemm": {"achieved": round(achieved, 2), "launches": n_launch,
+                              "kernel_ms_per_step": round(conv_ms / n_prof, 3),
+                              "gflop_per_step": round(conv_f / n_prof / 1e9, 2)},
+            "by_kind": detail}
+
+
+DUMP_BUDGET_BYTES = 48 << 20  # of the 64 MB a dump may take
+
+
+def dump_outputs(out_dir, model, losses):
+    """What a caller of train_step has after the last timed step: the loss it returned
+    (loss.npy; losses.npy holds every timed step's) and the parameters it updated in place
+    (param.<name>.npy).  A parameter larger than the per-tensor cap is written as a sample
+    at fixed positions (seeded by the parameter's index and size only), so the files of two
+    builds hold the same elements."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    all_losses = torch.stack(losses).double().reshape(-1).cpu().numpy()
+    np.save(os.path.join(out_dir, "loss.npy"), all_losses[-1:])
+    np.save(os.path.join(out_dir, "losses.npy"), all_losses)
+    params = [(k, p.detach()) for k, p in model.named_parameters()]
+    cap = 1 << 16
+    while sum(min(p.numel(), cap) for _, p in params) * 4 > DUMP_BUDGET_BYTES:
+        cap //= 2
+    for i, (k, p) in enumerate(params):
+        flat = p.reshape(-1)
+        if flat.numel() > cap:
+            rng = np.random.default_rng([i, flat.numel()])
+            idx = np.sort(rng.integers(0, flat.numel(), cap))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        np.save(os.path.join(out_dir, f"param.{k}.npy"), flat.float().cpu().numpy())
+
+
 def main():
     a = parse()
     from tlod.dist import GradBucketReducer, init_from_env
@@ -199,23 +288,26 @@ def main():
         beforehand (pool), so recording costs the host one hipEventRecord each."""
         pool = []
 
-    # launches per step, counted on one untimed step
-    probe = Records()
-    tconv.PROFILE = probe
-    train_step(model, opt, data.next(), reducer=reducer)
-    tconv.PROFILE = None
-    torch.cuda.synchronize()
-    # The per-launch events go on the LAST n_prof timed steps only (TLOD_BENCH_PROF_STEPS,
-    # default 1): an event pair on every launch of every step took 3% of the DAF-VGG16 step
-    # and 12% of the DAF-ResNet101 step (14.23 vs 13.81 ms, 21.47 vs 18.87 ms, one lease) —
-    # each timing event is a stream marker the GPU stops for.
+    # The per-launch events (--full) go on the LAST n_prof timed steps only
+    # (TLOD_BENCH_PROF_STEPS, default 1): an event pair on every launch of every step took 3%
+    # of the DAF-VGG16 step and 12% of the DAF-ResNet101 step (14.23 vs 13.81 ms, 21.47 vs
+    # 18.87 ms, back to back) — each timing event is a stream marker the GPU stops for.
     n_prof = max(1, min(a.steps, int(os.environ.get("TLOD_BENCH_PROF_STEPS", "1"))))
     records = Records()
-    records.pool = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                    for _ in range(len(probe) * n_prof + 64)]
-    del probe
-    # TLOD_BENCH_NOPROF=1 (diagnostic): no per-launch events at all (no roofline)
-    noprof = os.environ.get("TLOD_BENCH_NOPROF") == "1"
+    if a.full:
+        # launches per step, counted on one untimed step
+        probe = Records()
+        tconv.PROFILE = probe
+        train_step(model, opt, data.next(), reducer=reducer)
+        tconv.PROFILE = None
+        torch.cuda.synchronize()
+        records.pool = [(torch.cuda.Event(enable_timing=True),
+                         torch.cuda.Event(enable_timing=True))
+                        for _ in range(len(probe) * n_prof + 64)]
+        del probe
+    # a plain run, or TLOD_BENCH_NOPROF=1 under --full (diagnostic): no per-launch events
+    # at all (no roofline)
+    noprof = not a.full or os.environ.get("TLOD_BENCH_NOPROF") == "1"
     stats0 = dict(tconv.STATS)
     if world > 1:
         dist.barrier()
@@ -246,24 +338,6 @@ def main():
     value = world * a.steps / el  # one source image per rank per step
     last_loss = float(torch.stack(losses).float().mean().item())
 
-    achieved, detail, conv_ms, conv_f, n_launch, dom, fams = conv_roofline(records)
-    if dom is None:  # TLOD_BENCH_NOPROF: no launch records
-        dom = {"family": "none", "math": "bf16x6", "achieved": 0.0, "peak": 1.0, "ms": 0.0,
-               "launches": 1, "bytes": 0.0}
-    traffic, traffic_src = measured_traffic(a)
-    fam_kernels = {"conv3x3/bf16x6": ("conv_fwd_bs_kernel", "conv_fwd_bs_ws_kernel",
-                                      "wgrad_ws_kernel"),
-                   "conv3x3/f32": ("conv_fwd_kernel", "conv_wgrad_kernel"),
-                   "conv1x1/bf16x6": ("conv_gemm_bs_kernel", "conv_wgrad_bs_kernel"),
-                   "gemm/bf16x6": ("gemm_bs_kernel",)}
-    dom_kernels = fam_kernels.get(dom["family"], ())
-    per_launch_pmc = None
-    if traffic and dom_kernels:
-        by_k = traffic["bytes_per_step_by_kernel"]
-        # a PMC pass that predates a kernel of the family cannot price this run's launches
-        if all(k in by_k for k in dom_kernels if k != "conv_fwd_bs_kernel"):
-            per_launch_pmc = round(sum(by_k.get(k, 0) for k in dom_kernels) /
-                                   (dom["launches"] / n_prof))
     result = {
         "metric": METRIC.replace("DAF VGG16", f"{a.method.upper()} {'VGG16' if a.net == 'vgg16' else 'ResNet101'}"),
         "value": round(value, 4), "unit": "img/s", "n_gpus": world,
@@ -279,31 +353,7 @@ def main():
                    "classes": ncls, "rpn_pre_post_nms_train": [12000, 2000],
                    "rpn_pre_post_nms_test": [6000, 300],
                    "rcnn_batch": 256 if a.net == "vgg16" else 128},
-        "roofline": {"bound": "mfma", "achieved": round(dom["achieved"], 2),
-                     "peak": round(dom["peak"], 1), "unit": "TFLOP/s",
-                     "frac": round(dom["achieved"] / dom["peak"], 4),
-                     "traffic": per_launch_pmc,
-                     "algorithmic_bytes": round(dom["bytes"] / dom["launches"]),
-                     "traffic_source": traffic_src,
-                     "traffic_note": "PMC HBM bytes per launch of the dominant kernels "
-                                     f"({' + '.join(dom_kernels)}; FETCH_SIZE x2 + WRITE_SIZE) "
-                                     "vs algorithmic bytes per launch (operands read once, "
-                                     "result written once)" +
-                                     ("" if per_launch_pmc is not None or not traffic else
-                                      "; null: the committed PMC pass predates a kernel "
-                                      "of the family"),
-                     "traffic_by_kernel_per_step": (traffic or {}).get("bytes_per_step_by_kernel"),
-                     "kernel": f"tlod {dom['family']} (the family with the most time of "
-                               "the timed conv + GEMM launches)",
-                     "kernel_ms_per_step": round(dom["ms"] / n_prof, 3),
-                     "profiled_steps": n_prof,
-                     "families": fams,
-                     "peak_basis": "f32-equivalent: algorithmic f32 FLOPs at the MFMA peak; "
-                                   "bf16xN = 2516.6 TF bf16 dense / N products",
-                     "all_conv_gemm": {"achieved": round(achieved, 2), "launches": n_launch,
-                                  "kernel_ms_per_step": round(conv_ms / n_prof, 3),
-                                  "gflop_per_step": round(conv_f / n_prof / 1e9, 2)},
-                     "by_kind": detail},
+        "roofline": roofline_entry(a, records, n_prof) if a.full else None,
         "conv_math": {"3x3 fwd/dgrad": tconv.conv_math(), "3x3 and 1x1 wgrad": tconv.wgrad_math(),
                       "1x1 fwd/dgrad": f"{tconv.conv_math()} (>= 64 channels on one side, "
                                        ">= 16 on the other; f32 MFMA for the 2-output DA "
@@ -318,7 +368,9 @@ def main():
                                          for k, v in tconv.STATS.items()},
         "cpu_baseline": None,
     }
-    if rank == 0 and world == 1 and a.cpu_baseline_steps > 0 and a.method == "daf" \
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, model, losses)
+    if a.full and rank == 0 and world == 1 and a.cpu_baseline_steps > 0 and a.method == "daf" \
             and a.net == "vgg16":
         result["cpu_baseline"] = cpu_baseline(a.cpu_baseline_steps, a.height, a.width,
                                               a.cpu_threads)

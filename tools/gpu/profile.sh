@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
 export PYTHONUNBUFFERED=1
 rm -rf $O/stats $O/fetch $O/write $O/conv33_stats
-B="python3 bench.py --steps 10 --warmup 3 --cpu-baseline-steps 0"
+B="python3 bench.py --full --steps 10 --warmup 3 --cpu-baseline-steps 0"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o run -- $B > $O/bench_rocprof.json 2> $O/stats.err
 timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/fetch -o run -- $B > /dev/null 2> $O/fetch.err
 timeout -s KILL 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/write -o run -- $B > /dev/null 2> $O/write.err
@@ -19,7 +19,7 @@ TLOD_BENCH_SHAPES=1 timeout -k 10 200 $B > $O/bench_shapes.json 2> $O/bench_shap
 # BASELINE configs 3-5 (per GPU): DAF ResNet101, MAF VGG16, ATF ResNet101 (21 classes)
 for cfg in "daf res101" "maf vgg16" "atf res101"; do
   set -- $cfg
-  timeout -k 10 400 python3 bench.py --method $1 --net $2 --steps 10 --warmup 3 --cpu-baseline-steps 0 \
+  timeout -k 10 400 python3 bench.py --full --method $1 --net $2 --steps 10 --warmup 3 --cpu-baseline-steps 0 \
     > $O/bench_$1_$2.json 2> $O/bench_$1_$2.err
 done
 if [ -n "$P" ]; then

@@ -20,6 +20,6 @@ else
   bash tools/gpu/pmc_conv.sh $O/pmc > /dev/null 2>&1 || true
   cp $O/pmc/p1.txt $P/pmc_conv3_3_mfma_busy.txt || true
   cp $O/pmc/p2.txt $P/pmc_conv3_3_lds.txt || true
-  timeout -k 10 400 python3 bench.py > $P/bench_line.json 2> $O/bench_line.err
+  timeout -k 10 400 python3 bench.py --full > $P/bench_line.json 2> $O/bench_line.err
   cat $P/bench_line.json
 fi

@@ -8,5 +8,5 @@ timeout -k 10 1000 python3 -u -m pytest tests -m gpu -x -q --timeout 300 --timeo
 tail -3 $O/pytest.log
 timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1
 tail -1 $O/smoke.log
-timeout -k 10 400 python3 bench.py > $O/bench.json 2> $O/bench.err
+timeout -k 10 400 python3 bench.py --full > $O/bench.json 2> $O/bench.err
 cat $O/bench.json

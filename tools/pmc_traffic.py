@@ -42,7 +42,7 @@ def main():
     per = {k: (2.0 * fetch.get(k, 0.0) + write.get(k, 0.0)) / steps for k in keys}
     per = dict(sorted(((k, round(v)) for k, v in per.items() if v >= 1e5), key=lambda kv: -kv[1]))
     res = {"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE passes (separate runs) over "
-                     "python3 bench.py --steps 10 --warmup 3 --cpu-baseline-steps 0",
+                     "python3 bench.py --full --steps 10 --warmup 3 --cpu-baseline-steps 0",
            "steps_profiled": steps,
            "correction": "FETCH_SIZE x2 (gfx950 wide-read undercount), KiB -> B",
            "bytes_per_step_by_kernel": per, "bytes_per_step": round(sum(per.values()))}
