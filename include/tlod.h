@@ -128,6 +128,38 @@ int tlod_roi_pool_fwd_f32(const float* feat, int B, int C, int H, int W,
 int tlod_roi_pool_bwd_f32(const float* top_grad, const int32_t* argmax, int R, int C,
                           int ph, int pw, float* bottom_grad, tlod_stream_t stream);
 
+/* ------------------------------------------------------------------ RoI crop
+ * Replaces: BilinearSamplerBHWD_updateOutput_cuda / _updateGradInput_cuda
+ *   lib/model/roi_crop/src/roi_crop_cuda.c (kernels roi_crop_cuda_kernel.cu:11-194), and, for
+ *   the *_pool pair, the whole POOLING_MODE 'crop' branch of faster_rcnn.py:73-81
+ *   (net_utils._affine_grid_gen, the (y, x) swap, _RoICrop, F.max_pool2d(2, 2)).
+ * x (B,C,H,W) with H, W >= 2.  No workspace; fwd writes every output (a sample whose four
+ * taps are all outside the map is 0), bwd OVERWRITES grad_in (B,C,H,W) (no pre-zeroing) with
+ * the input gradient only — the reference kernel never writes the grid gradient, which is 0.
+ * Both backwards are gathers in a fixed order (no atomics): bit-identical from run to run.
+ *
+ * tlod_roi_crop_*: the sampler over a caller's grid (R,gh,gw,2) in (y, x) order, values in
+ * [-1, 1] spanning the map's cell centres; grid r samples image r / (R / B) (R % B == 0).
+ * out / grad_out (R,C,gh,gw).
+ *
+ * tlod_roi_crop_pool_*: rois (R,5) = (batch, x1, y1, x2, y2) in image coords; theta, the
+ * G x G grid (G = 2P with max_pool, else P; G <= 32), the samples and the 2x2 max in one
+ * kernel.  out / grad_out (R,C,P,P); argmax (R,C,P,P), one byte: which of the four pooled
+ * samples won (row-major, the first on ties, as F.max_pool2d); may be NULL when max_pool = 0.
+ * The image is rois[:, 0] (not r / (R / B)): images may own different numbers of RoIs, and
+ * the result equals the reference's whenever its equal-count layout holds.  A RoI whose
+ * index is outside [0, B) reads nothing: its outputs are 0 and it adds no gradient. */
+int tlod_roi_crop_fwd_f32(const float* x, int B, int C, int H, int W, const float* grid, int R,
+                          int gh, int gw, float* out, tlod_stream_t stream);
+int tlod_roi_crop_bwd_f32(const float* grad_out, const float* grid, int R, int C, int gh, int gw,
+                          int B, int H, int W, float* grad_in, tlod_stream_t stream);
+int tlod_roi_crop_pool_fwd_f32(const float* x, int B, int C, int H, int W, const float* rois,
+                               int R, int P, float spatial_scale, int max_pool, float* out,
+                               uint8_t* argmax, tlod_stream_t stream);
+int tlod_roi_crop_pool_bwd_f32(const float* grad_out, const uint8_t* argmax, int B, int C, int H,
+                               int W, const float* rois, int R, int P, float spatial_scale,
+                               int max_pool, float* grad_in, tlod_stream_t stream);
+
 /* ------------------------------------------------------------------ Proposal layer
  * Replaces: _ProposalLayer.forward   lib/model/rpn/proposal_layer.py:49-161
  * cls_prob (B,2A,H,W) (fg = channels A..2A-1), bbox_deltas (B,4A,H,W), im_info (B,3),

@@ -1,6 +1,9 @@
-"""Microbenchmark: RoIAlignAvg 7x7 backward on the DAF step's shape (2 images, base feature
-512 x 37 x 75, 256 source + 300 target RoIs of realistic sizes): the sorted-tap gather
-(default, no atomics), TLOD_ROI_BWD_GATHER=0 the global-atomic NHWC kernel."""
+"""Microbenchmark of the RoI pooling kernels on the DAF step's shape (2 images, base feature
+512 x 37 x 75, 256 source + 300 target RoIs of realistic sizes): RoIAlignAvg 7x7 forward and
+backward (the sorted-tap gather by default, no atomics; TLOD_ROI_BWD_GATHER=0 the
+global-atomic NHWC kernel), and the fused RoI crop + max-pool (POOLING_MODE 'crop', P = 7)
+forward and backward, beside the unfused crop composition (affine_grid_gen + _RoICrop +
+max_pool2d) for the same RoIs."""
 import json
 import os
 import sys
@@ -34,23 +37,76 @@ def main():
               L.tlod_roi_align_avg_bwd_workspace_bytes(B, C, H, W))
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
 
-    def run():
+    def timed(fn, n=20):
+        for _ in range(3):
+            fn()
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        s.record()
+        for _ in range(n):
+            fn()
+        e.record()
+        torch.cuda.synchronize()
+        return round(s.elapsed_time(e) / n * 1e3, 1)
+
+    feat = torch.randn(B, C, H, W, device=dev)
+    out = torch.empty(R, C, 7, 7, device=dev)
+    st = _lib.stream_of(top)
+
+    def align_fwd():
+        _lib.check(L.tlod_roi_align_avg_fwd_f32(_lib.ptr(feat), B, C, H, W, _lib.ptr(r), R, 7, 7,
+                                                1.0 / 16, _lib.ptr(out), st), "roi_align_avg_fwd")
+
+    def align_bwd():
         _lib.check(L.tlod_roi_align_avg_bwd_f32(_lib.ptr(top), B, C, H, W, _lib.ptr(r), R, 7, 7,
                                                 1.0 / 16, _lib.ptr(grad), _lib.ptr(ws), ws.numel(),
-                                                _lib.stream_of(top)), "roi_align_avg_bwd")
-    for _ in range(3):
-        run()
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    s.record()
-    for _ in range(20):
-        run()
-    e.record()
-    torch.cuda.synchronize()
-    us = s.elapsed_time(e) / 20 * 1e3
+                                                st), "roi_align_avg_bwd")
+
+    argmax = torch.empty(R, C, 7, 7, dtype=torch.uint8, device=dev)
+
+    def crop_fwd():
+        _lib.check(L.tlod_roi_crop_pool_fwd_f32(_lib.ptr(feat), B, C, H, W, _lib.ptr(r), R, 7,
+                                                1.0 / 16, 1, _lib.ptr(out), _lib.ptr(argmax), st),
+                   "roi_crop_pool_fwd")
+
+    def crop_bwd():
+        _lib.check(L.tlod_roi_crop_pool_bwd_f32(_lib.ptr(top), _lib.ptr(argmax), B, C, H, W,
+                                                _lib.ptr(r), R, 7, 1.0 / 16, 1, _lib.ptr(grad), st),
+                   "roi_crop_pool_bwd")
+
     kind = "atomic" if os.environ.get("TLOD_ROI_BWD_GATHER") == "0" else "gather"
-    print(json.dumps({"kernel": kind, "roi_align_avg_bwd_us": round(us, 1),
-                      "R": R, "C": C, "map": [H, W]}))
+    res = {"kernel": kind, "roi_align_avg_fwd_us": timed(align_fwd),
+           "roi_align_avg_bwd_us": timed(align_bwd), "roi_crop_pool_fwd_us": timed(crop_fwd),
+           "roi_crop_pool_bwd_us": timed(crop_bwd)}
+
+    # the unfused composition (the general sampler needs equal RoI counts per image, in order:
+    # the first 256 RoIs of each image)
+    import torch.nn.functional as F
+    from tlod.roi_crop import _RoICrop, affine_grid_gen
+    re = torch.cat([r[:256], r[256:512]], 0)
+    fx = feat.clone().requires_grad_()
+    sampler = _RoICrop()
+    state = {}
+
+    def comp_fwd():
+        gxy = affine_grid_gen(re, (H, W), 14)
+        gyx = torch.stack([gxy[..., 1], gxy[..., 0]], 3).contiguous()
+        state["y"] = F.max_pool2d(sampler(fx, gyx), 2, 2)
+
+    def comp_bwd():
+        fx.grad = None
+        state["y"].backward(top[:512], retain_graph=True)
+
+    res["unfused_crop_fwd_us_512rois"] = timed(comp_fwd, 5)
+    res["unfused_crop_bwd_us_512rois"] = timed(comp_bwd, 5)
+    # HBM bytes: what the fused forward moves at least (map + rois in, out + argmax out), and
+    # what the unfused composition writes and reads back on top of that for the same R (the
+    # grid and its (y, x)-swapped copy, the (R, C, 14, 14) sample map)
+    grid_bytes, map_bytes = R * 14 * 14 * 2 * 4, R * C * 14 * 14 * 4
+    res["fused_fwd_min_bytes"] = 4 * B * C * H * W + 20 * R + 5 * R * C * 49
+    res["unfused_fwd_extra_bytes"] = 2 * (2 * grid_bytes + map_bytes)
+    res.update({"R": R, "C": C, "map": [H, W]})
+    print(json.dumps(res))
 
 
 if __name__ == "__main__":

@@ -87,6 +87,13 @@ SIGNATURES = {
     "tlod_roi_pool_fwd_f32": (c_int, [P, c_int, c_int, c_int, c_int, P, c_int, c_int, c_int,
                                       c_float, P, P, P]),
     "tlod_roi_pool_bwd_f32": (c_int, [P, P, c_int, c_int, c_int, c_int, P, P]),
+    "tlod_roi_crop_fwd_f32": (c_int, [P, c_int, c_int, c_int, c_int, P, c_int, c_int, c_int, P, P]),
+    "tlod_roi_crop_bwd_f32": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P,
+                                      P]),
+    "tlod_roi_crop_pool_fwd_f32": (c_int, [P, c_int, c_int, c_int, c_int, P, c_int, c_int,
+                                           c_float, c_int, P, P, P]),
+    "tlod_roi_crop_pool_bwd_f32": (c_int, [P, P, c_int, c_int, c_int, c_int, P, c_int, c_int,
+                                           c_float, c_int, P, P]),
     "tlod_proposal_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "tlod_proposal_f32": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                   c_float, P, P, P, c_size_t, P]),

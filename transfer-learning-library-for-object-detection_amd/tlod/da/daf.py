@@ -26,6 +26,7 @@ from ..detector.losses import (daf_da_losses, daf_da_losses_packed, fused_losses
                                smooth_l1_loss, weighted_loss_sum)
 from ..detector.vgg16 import vgg16_base, vgg16_top
 from ..roi_align import RoIAlignAvg
+from ..roi_crop import RoICropPool
 from ..roi_pool import _RoIPooling
 from ..rpn.proposal import proposals_on_side_streams
 from ..rpn.proposal_target import _ProposalTargetLayer
@@ -157,6 +158,8 @@ class _fasterRCNN(nn.Module):
         self.RCNN_proposal_target = _ProposalTargetLayer(self.n_classes)
         self.RCNN_roi_pool = _RoIPooling(cfg.POOLING_SIZE, cfg.POOLING_SIZE, 1.0 / 16.0)
         self.RCNN_roi_align = RoIAlignAvg(cfg.POOLING_SIZE, cfg.POOLING_SIZE, 1.0 / 16.0)
+        self.RCNN_roi_crop_pool = RoICropPool(cfg.POOLING_SIZE, 1.0 / 16.0,
+                                              cfg.CROP_RESIZE_WITH_MAX_POOL)
         self.RCNN_imageDA = _ImageDA(self.dout_base_model)
         self.RCNN_instanceDA = _InstanceDA(self.instance_dim)
         self.consistency_loss = nn.MSELoss(reduction="sum")
@@ -169,7 +172,10 @@ class _fasterRCNN(nn.Module):
             return self.RCNN_roi_align(feat, rois)
         if cfg.POOLING_MODE == "pool":
             return self.RCNN_roi_pool(feat, rois)
-        raise NotImplementedError("POOLING_MODE 'crop' is out of scope (configs use 'align')")
+        if cfg.POOLING_MODE == "crop":
+            # faster_rcnn.py:73-81 reads the max-pool switch at every forward
+            return self.RCNN_roi_crop_pool(feat, rois, max_pool=cfg.CROP_RESIZE_WITH_MAX_POOL)
+        raise ValueError(f"unknown POOLING_MODE {cfg.POOLING_MODE!r}")
 
     def _rcnn_losses(self, pooled_s, rois_label, rois_target, rois_inside_ws, rois_outside_ws):
         """Head outputs and losses of the first rois_label.numel() rows of ``pooled_s``

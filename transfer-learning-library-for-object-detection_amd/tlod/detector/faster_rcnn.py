@@ -18,6 +18,7 @@ import torch.nn.functional as F
 
 from ..config import cfg
 from ..roi_align import RoIAlignAvg
+from ..roi_crop import RoICropPool
 from ..roi_pool import _RoIPooling
 from ..rpn.proposal import proposals_on_side_streams
 from ..rpn.proposal_target import _ProposalTargetLayer
@@ -40,6 +41,8 @@ class _fasterRCNN(nn.Module):
         self.RCNN_proposal_target = _ProposalTargetLayer(self.n_classes)
         self.RCNN_roi_pool = _RoIPooling(cfg.POOLING_SIZE, cfg.POOLING_SIZE, 1.0 / 16.0)
         self.RCNN_roi_align = RoIAlignAvg(cfg.POOLING_SIZE, cfg.POOLING_SIZE, 1.0 / 16.0)
+        self.RCNN_roi_crop_pool = RoICropPool(cfg.POOLING_SIZE, 1.0 / 16.0,
+                                              cfg.CROP_RESIZE_WITH_MAX_POOL)
         self.replay_rng = None  # tests: np.random-like object -> reference-exact sampling
         self.capture = None     # tests: dict receiving the proposal-layer rois
 
@@ -48,7 +51,10 @@ class _fasterRCNN(nn.Module):
             return self.RCNN_roi_align(feat, rois)
         if cfg.POOLING_MODE == "pool":
             return self.RCNN_roi_pool(feat, rois)
-        raise NotImplementedError("POOLING_MODE 'crop' is out of scope (configs use 'align')")
+        if cfg.POOLING_MODE == "crop":
+            # faster_rcnn.py:73-81 reads the max-pool switch at every forward
+            return self.RCNN_roi_crop_pool(feat, rois, max_pool=cfg.CROP_RESIZE_WITH_MAX_POOL)
+        raise ValueError(f"unknown POOLING_MODE {cfg.POOLING_MODE!r}")
 
     def forward(self, im_data, im_info, gt_boxes, num_boxes):
         batch_size = im_data.size(0)
