@@ -579,6 +579,66 @@ int tlod_sgd_clip_pack_f32(const tlod_sgd_chunk* chunks, int n_chunks, int n_upd
                            float momentum, float clip_norm, float* partials, float* norm_scale,
                            tlod_stream_t stream);
 
+/* The same step with torch.optim.Adam's update (its defaults: L2 weight decay added to the
+ * gradient, no amsgrad, no maximize) in place of SGD's — the reference's `--o adam`
+ * (methods/DAF/DAF_train.py:320-325).  With g' the scaled, clipped gradient as above and t
+ * the parameter's own step count after this step:
+ *   d = g' + wd*p; m = b1*m + (1-b1)*d; v = b2*v + (1-b2)*d*d;
+ *   p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps).
+ * states: device array of n_states rows, exactly one per parameter that has rows in chunks.
+ * Between the norm and the update, every row whose *active != 0 (or active == NULL) gets
+ * *step += 1 and corr[0..1] = (1 / (1 - b1^t), 1 / sqrt(1 - b2^t)), computed in double; the
+ * parameter's chunk and tile rows point at the same corr pair.  A parameter whose *active
+ * == 0 keeps p, m, v and its step count untouched, like a None .grad in torch.optim.Adam.
+ * Nothing that changes from step to step is stored in the tables, so they can be cached.
+ * exp_avg / exp_avg_sq start at 0, *step at 0.  count < 0, n_update, tiles, partials and
+ * norm_scale as for tlod_sgd_clip_pack_f32.  beta1, beta2 in [0, 1), eps > 0. */
+typedef struct tlod_adam_chunk {
+  float* param;
+  const float* grad;
+  float* exp_avg;
+  float* exp_avg_sq;
+  long long count;
+  float lr;
+  float weight_decay;
+  const float* active;
+  const float* corr;
+} tlod_adam_chunk;
+
+typedef struct tlod_adam_pack_tile {
+  float* param;
+  const float* grad;
+  float* exp_avg;
+  float* exp_avg_sq;
+  const float* active;
+  const float* corr;
+  unsigned short* pack_fwd;
+  unsigned short* pack_dgrad;
+  unsigned short* pack_dgrad_scaled;
+  const float* scale;
+  float lr;
+  float weight_decay;
+  int cout, cin;
+  int o0, i0;
+} tlod_adam_pack_tile;
+
+typedef struct tlod_adam_state {
+  int* step;
+  const float* active;
+  float* corr;
+} tlod_adam_state;
+
+int tlod_adam_clip_pack_f32(const tlod_adam_chunk* chunks, int n_chunks, int n_update,
+                            const tlod_adam_pack_tile* tiles, int n_tiles,
+                            const tlod_adam_state* states, int n_states, float grad_scale,
+                            double beta1, double beta2, double eps, float clip_norm,
+                            float* partials, float* norm_scale, tlod_stream_t stream);
+
+/* tlod_adam_clip_pack_f32 without tiles: every chunk row is updated. */
+int tlod_adam_clip_f32(const tlod_adam_chunk* chunks, int n_chunks, const tlod_adam_state* states,
+                       int n_states, float grad_scale, double beta1, double beta2, double eps,
+                       float clip_norm, float* partials, float* norm_scale, tlod_stream_t stream);
+
 /* ------------------------------------------------------------------ Input blob
  * Replaces: the data layer's per-image host chain — scipy imread (RGB) -> BGR -> flip
  *   (lib/roi_data_layer/minibatch.py:62-82) -> astype(float32) -= PIXEL_MEANS ->

@@ -1,7 +1,8 @@
-"""Optimizer step microbench: the fused clip + SGD over DAF-VGG16-shaped trainable parameters,
-with the 3x3 weight packs either written by the update's tiles (TLOD_SGD_PACK=1) or made by
+"""Optimizer step microbench: the fused clip + SGD (or, with --optimizer adam, clip + Adam) over
+DAF-VGG16-shaped trainable parameters, with the 3x3 weight packs either written by the update's tiles (TLOD_SGD_PACK=1) or made by
 tlod_conv_pack_bs launches before the next use (0: one fwd + one dgrad pack per weight, as
 the step does).  Prints JSON: ms per step (step + packs) and the kernel split."""
+import argparse
 import json
 import os
 import sys
@@ -13,8 +14,11 @@ sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..",
 
 
 def main():
+    ap = argparse.ArgumentParser(description=__doc__)
+    ap.add_argument("--optimizer", choices=("sgd", "adam"), default="sgd")
+    args = ap.parse_args()
     from tlod import conv
-    from tlod.optim import FusedSGDClip
+    from tlod.optim import FusedAdamClip, FusedSGDClip
     torch.manual_seed(0)
     convs = [(256, 128), (256, 256), (256, 256), (512, 256), (512, 512), (512, 512),
              (512, 512), (512, 512), (512, 512), (512, 512)]
@@ -24,8 +28,9 @@ def main():
     bs = [torch.nn.Parameter(torch.zeros(co, device="cuda")) for co, _ in convs]
     params = ws + fcs + bs
     fused = os.environ.get("TLOD_SGD_PACK", "1") != "0"
-    opt = FusedSGDClip([{"params": ws + fcs, "lr": 1e-3, "weight_decay": 5e-4},
-                        {"params": bs, "lr": 2e-3, "weight_decay": 0.0}], clip_norm=10.0)
+    cls = FusedAdamClip if args.optimizer == "adam" else FusedSGDClip
+    opt = cls([{"params": ws + fcs, "lr": 1e-3, "weight_decay": 5e-4},
+               {"params": bs, "lr": 2e-3, "weight_decay": 0.0}], clip_norm=10.0)
     for p in params:
         p.grad = torch.randn_like(p) * 1e-3
 
@@ -48,7 +53,7 @@ def main():
         packs()
     e1.record()
     torch.cuda.synchronize()
-    print(json.dumps({"fused_packs": fused, "ms_per_step": round(e0.elapsed_time(e1) / n, 4),
+    print(json.dumps({"optimizer": args.optimizer, "fused_packs": fused, "ms_per_step": round(e0.elapsed_time(e1) / n, 4),
                       "params": sum(p.numel() for p in params),
                       "conv3x3_params": sum(w.numel() for w in ws)}))
 

@@ -4,7 +4,7 @@ synthetic Cityscapes->Foggy batch source used by bench.py / smoke().
 Per step (one source + one target image): forward -> loss sum with lamda * DA terms
 (:397-400) -> backward -> clip_gradient(10) for VGG16 (:406-407, here device-side with
 no .item()) -> SGD(momentum 0.9; biases 2x lr, no weight decay; weights lr, wd 5e-4)
-(:311-325).  Optional gradient all-reduce hook (tlod.dist) runs inside backward.
+(:311-325), or Adam over the same groups (``--o adam``, :320-325).  Optional gradient all-reduce hook (tlod.dist) runs inside backward.
 """
 import math
 
@@ -49,10 +49,14 @@ def build_daf_vgg16(device, classes=CITYSCAPES_CLASSES, seed=0):
 
 
 def make_optimizer(model, lr, momentum=None, weight_decay=None, double_bias=None, bias_decay=None,
-                   fused=True, clip=None):
+                   fused=True, clip=None, optimizer="sgd", betas=None, eps=None):
     """DAF_train.py:311-325 param groups (collapsed to two groups — same update).
-    fused=True: libtlod's fused clip_gradient(clip) + SGD (tlod.optim.FusedSGDClip).
+    optimizer: "sgd" or "adam" (the reference's --o; Adam with torch's defaults unless betas /
+    eps are given).  fused=True: libtlod's fused clip_gradient(clip) + update
+    (tlod.optim.FusedSGDClip / FusedAdamClip); fused=False: the torch optimizer.
     clip None: 10 for VGG16, none for ResNet101 (DAF_train.py:406-407)."""
+    if optimizer not in ("sgd", "adam"):
+        raise ValueError(f"unknown optimizer {optimizer!r} (have 'sgd', 'adam')")
     if clip is None:
         clip = default_clip(model)
     momentum = cfg.TRAIN.MOMENTUM if momentum is None else momentum
@@ -66,6 +70,16 @@ def make_optimizer(model, lr, momentum=None, weight_decay=None, double_bias=None
     groups = [{"params": weights, "lr": lr, "weight_decay": wd},
               {"params": biases, "lr": lr * (double_bias + 1),
                "weight_decay": wd if bias_decay else 0.0}]
+    if optimizer == "adam":
+        kw = {}
+        if betas is not None:
+            kw["betas"] = tuple(betas)
+        if eps is not None:
+            kw["eps"] = eps
+        if fused:
+            from ..optim import FusedAdamClip
+            return FusedAdamClip(groups, clip_norm=clip, **kw)
+        return torch.optim.Adam(groups, lr=lr, **kw)
     if fused:
         from ..optim import FusedSGDClip
         return FusedSGDClip(groups, momentum=momentum, clip_norm=clip)
@@ -139,8 +153,8 @@ def default_clip(model):
 def train_step(model, optimizer, batch, lamda=0.1, clip=None, reducer=None):
     """One DAF/MAF/ATF iteration (the method's own loss sum, model.total_loss); returns the
     loss as a device tensor (no host sync)."""
-    from ..optim import FusedSGDClip
-    fused = isinstance(optimizer, FusedSGDClip)
+    from ..optim import FusedClipOptimizer
+    fused = isinstance(optimizer, FusedClipOptimizer)
     if reducer is not None:
         reducer.zero_grad()  # grads are views into the arena the reducer all-reduces
     else:
@@ -153,7 +167,7 @@ def train_step(model, optimizer, batch, lamda=0.1, clip=None, reducer=None):
         reducer.finish(scale=not fused)  # SUM all-reduce; the fused step applies 1/world
         scale = reducer.grad_scale
     if fused:
-        optimizer.step(grad_scale=scale)  # clip_gradient + SGD fused
+        optimizer.step(grad_scale=scale)  # clip_gradient + SGD / Adam fused
     else:
         clip = default_clip(model) if clip is None else clip
         if clip:
