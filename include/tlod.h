@@ -766,6 +766,57 @@ int tlod_da_loss_bwd_f32(const float* score_s, const float* score_t, const float
                          const float* grad_loss, const float* cons, float* dscore_s,
                          float* dscore_t, float* dins_s, float* dins_t, tlod_stream_t stream);
 
+/* ------------------------------------------------------------------ PT-MAF
+ * Replaces: the torch.where / full_like maps, the masked nll_loss terms, the softmax / log /
+ *   quotient KL sums and the host double loop over feature cells of lib/PT_MAF and
+ *   methods/PT_MAF (faster_rcnn.py:132-148, 290-398; PT_MAF_train.py:444-456;
+ *   faster_rcnn_kd.py:58-65).  One launch per call, no host synchronisation; element
+ *   arithmetic fp32 (double inside a KD row), sums in a fixed order (double accumulators,
+ *   one workgroup per reduction), cell counts in integers: results are bit-identical from
+ *   run to run.
+ *
+ * Foreground / background maps: prob (B, 2A, H, W) RPN probabilities, channels A..2A-1 the
+ *   object probabilities.  Per image: t = max over those channels, m = max t,
+ *   f = t > m * high, b = t < m * low (strict; one fp32 multiply each).  f, b (B, H, W) as
+ *   0 / 1 floats; stats (B, 5) = [m, sum f, sum b, sum f / (sum f + sum b),
+ *   sum b / (sum f + sum b)] (both ratios 0 if both maps are empty: high >= 1 only). */
+int tlod_fgbg_maps_f32(const float* prob, int B, int A, int H, int W, float high, float low,
+                       float* f, float* b, float* stats, tlod_stream_t stream);
+/* Masked two-way NLL of K <= 8 (score, map) pairs of one H x W level: scores[k] (B, 2, H, W)
+ *   domain logits, maps[k] (B, H, W) 0 / 1 (host arrays of K device pointers; a pointer may
+ *   repeat), need (B) the per-image domain label as float (need_backprop).
+ *   loss[k * B + b] = mean over maps[k][b] == 1 of -log_softmax(scores[k][b])[need[b]], and 0
+ *   for an empty map; count[k * B + b] = the map's cell count (saved for the backward).
+ *   Backward: dscores[k] = map * (softmax - onehot) * grad_loss[k * B + b] / count, all 0
+ *   for an empty map; every element of every dscores[k] is written, so the K gradient
+ *   buffers must be distinct even where scores repeat. */
+int tlod_masked_nll2_f32(const float* const* scores, const float* const* maps, int K,
+                         const float* need, int B, int H, int W, float* loss, float* count,
+                         tlod_stream_t stream);
+int tlod_masked_nll2_bwd_f32(const float* const* scores, const float* const* maps, int K,
+                             const float* need, int B, int H, int W, const float* grad_loss,
+                             const float* count, float* const* dscores, tlod_stream_t stream);
+/* Distillation KL at temperature T over R rows of C classes: element (r, c) of student /
+ *   teacher / dstudent is x[r * row_stride + c * class_stride]; row r's weight is
+ *   weight[r % wmod].  (R, C) contiguous RoI scores: strides (C, 1), wmod = R.  The RPN's
+ *   two-way scores (2, A*H*W): R = A*H*W, strides (1, A*H*W), wmod = H*W — the cell map
+ *   g (H, W) is expanded over the anchors by index.  p = softmax(x / T) in log-sum-exp form.
+ *   out[0] = sum_r w_r KL(p_student_r || p_teacher_r) / (sum w + 1), out[1] = sum w + 1
+ *   (saved for the backward); sum w is over the wmod weights, each counted once.  Backward, student only: dstudent[r, j] = grad_loss[0] * w_r /
+ *   (sum w + 1) / T * p1_j (log p1_j - log p2_j - KL_r); every element is written. */
+int tlod_kd_kl_f32(const float* student, const float* teacher, const float* weight, int R, int C,
+                   long long row_stride, long long class_stride, int wmod, float T, float* out,
+                   tlod_stream_t stream);
+int tlod_kd_kl_bwd_f32(const float* student, const float* teacher, const float* weight, int R,
+                       int C, long long row_stride, long long class_stride, int wmod, float T,
+                       const float* grad_loss, const float* aux, float* dstudent,
+                       tlod_stream_t stream);
+/* Ground-truth cell mask (faster_rcnn_kd.py:58-65): gt_boxes (G, 5), num_boxes one int64 on
+ *   the device.  g (H, W): cell (j, i) is 1 when int(x1 / 16) <= i < int(x2 / 16) and
+ *   int(y1 / 16) <= j < int(y2 / 16) for one of the first min(num_boxes, G) boxes. */
+int tlod_gt_cell_mask_f32(const float* gt_boxes, const long long* num_boxes, int G, int H, int W,
+                          float* g, tlod_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

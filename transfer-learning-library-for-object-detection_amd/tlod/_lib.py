@@ -207,6 +207,14 @@ SIGNATURES = {
                                        P, P, P]),
     "tlod_da_loss_f32": (c_int, [P, P, P, P, P, P] + [c_int] * 8 + [P, P, P]),
     "tlod_da_loss_bwd_f32": (c_int, [P, P, P, P, P, P] + [c_int] * 8 + [P, P, P, P, P, P, P]),
+    "tlod_fgbg_maps_f32": (c_int, [P, c_int, c_int, c_int, c_int, c_float, c_float, P, P, P, P]),
+    "tlod_masked_nll2_f32": (c_int, [P, P, c_int, P, c_int, c_int, c_int, P, P, P]),
+    "tlod_masked_nll2_bwd_f32": (c_int, [P, P, c_int, P, c_int, c_int, c_int, P, P, P, P]),
+    "tlod_kd_kl_f32": (c_int, [P, P, P, c_int, c_int, ctypes.c_longlong, ctypes.c_longlong,
+                               c_int, c_float, P, P]),
+    "tlod_kd_kl_bwd_f32": (c_int, [P, P, P, c_int, c_int, ctypes.c_longlong, ctypes.c_longlong,
+                                   c_int, c_float, P, P, P, P]),
+    "tlod_gt_cell_mask_f32": (c_int, [P, P, c_int, c_int, c_int, P, P]),
 }
 
 _lib = None

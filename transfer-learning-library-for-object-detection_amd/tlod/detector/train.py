@@ -16,14 +16,15 @@ from ..config import cfg, setup_training_cfg
 from ..data.imdb import CITYSCAPE_CLASSES as CITYSCAPES_CLASSES  # cityscape.py:51-54
 
 
-METHODS = ("faster_rcnn", "daf", "maf", "atf")
+METHODS = ("faster_rcnn", "daf", "maf", "atf", "pt_maf")
 
 
 def build_model(method, device, net="vgg16", classes=CITYSCAPES_CLASSES, seed=0,
                 dataset="cityscape"):
     """<method>.<net>(classes).create_architecture() (methods/<M>/<M>_train.py), random
     init (the pretrained caffe weights are external downloads).  method "faster_rcnn" is
-    the source-only detector (lib/model/faster_rcnn, methods/faster_rcnn)."""
+    the source-only detector (lib/model/faster_rcnn, methods/faster_rcnn); it is also
+    PT-MAF's teacher (put it in eval mode)."""
     if method not in METHODS:
         raise ValueError(f"unknown method {method!r} (have {METHODS})")
     if net not in ("vgg16", "res101"):
@@ -170,6 +171,38 @@ def train_step(model, optimizer, batch, lamda=0.1, clip=None, reducer=None):
         optimizer.step(grad_scale=scale)  # clip_gradient + SGD / Adam fused
     else:
         clip = default_clip(model) if clip is None else clip
+        if clip:
+            clip_gradient_([p for p in model.parameters()], clip)
+        optimizer.step()
+    return loss.detach()
+
+
+def pt_maf_train_step(model, teacher, optimizer, batch, lamda=0.1, T=3.0, high=0.7, low=0.1,
+                       alpha=1.0, beta=1.0, gamma=1.0, reducer=None):
+    """One PT-MAF iteration (methods/PT_MAF/PT_MAF_train.py:434-464): the student's forward,
+    the frozen teacher (a tlod.detector.faster_rcnn.vgg16 in eval mode, under no_grad and
+    unknown to the optimizer) on the source image and the student's sampled RoIs, the loss
+    sum with the KD term, backward, then as train_step.  Returns the loss as a device tensor
+    (no host sync)."""
+    from ..da.pt_maf import kd_loss, kd_teacher
+    from ..optim import FusedClipOptimizer
+    fused = isinstance(optimizer, FusedClipOptimizer)
+    if reducer is not None:
+        reducer.zero_grad()
+    else:
+        optimizer.zero_grad(set_to_none=True)
+    out = model(*batch, T=T, high=high, low=low, alpha=alpha, beta=beta, gamma=gamma)
+    teacher_out = kd_teacher(teacher, batch[0], batch[1], batch[2], batch[3], out[0], T)
+    loss = model.total_loss(out, lamda, kd_loss(model, teacher_out, out[7], T))
+    loss.backward()
+    scale = 1.0
+    if reducer is not None:
+        reducer.finish(scale=not fused)
+        scale = reducer.grad_scale
+    if fused:
+        optimizer.step(grad_scale=scale)
+    else:
+        clip = default_clip(model)
         if clip:
             clip_gradient_([p for p in model.parameters()], clip)
         optimizer.step()
