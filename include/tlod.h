@@ -817,6 +817,46 @@ int tlod_kd_kl_bwd_f32(const float* student, const float* teacher, const float* 
 int tlod_gt_cell_mask_f32(const float* gt_boxes, const long long* num_boxes, int G, int H, int W,
                           float* g, tlod_stream_t stream);
 
+/* ------------------------------------------------------------------ US-DAF
+ * Replaces: the per-RoI Python loops behind the scale labels (four device scalars read per
+ *   row) and the torch temporaries of nn.BCELoss / BCEloss_margin in lib/US_DAF
+ *   (faster_rcnn.py:25-33, 104-126, 207-231, 265-282).  One launch per call, no host
+ *   synchronisation.  The sigmoid is evaluated in double from the fp32 logit and rounded once
+ *   (the saved s is the correctly rounded fp32 sigmoid); all other element arithmetic is fp32
+ *   from that s; sums in a fixed order (double accumulators, one workgroup per domain):
+ *   results are bit-identical from run to run.  Every output element is written.
+ *
+ * RoI scale labels: rois (R, 5) = [batch, x1, y1, x2, y2]; labels (R, 3) 0 / 1 floats
+ *   [small, middle, large] from area = (x2 - x1) * (y2 - y1) in fp32 (no +1): area <= 400,
+ *   400 < area < 10000, area >= 10000 (a zero-padded row is small; a NaN area gets none). */
+int tlod_roi_scale_labels_f32(const float* rois, int R, float* labels, tlod_stream_t stream);
+/* US-DAF domain losses of the source (s, domain label 1) and target (t, label 0) domains:
+ *   z_img (B, 1, H, W) image-head logits, z_ins (n, 4) instance-head logits [domain, small,
+ *   middle, large], rois (n, 5).  The two domains' tensors may be slices of one buffer.
+ *   s = sigmoid(z) is written to s_img / s_ins (saved for the backward).
+ *   loss[0] / loss[2] = source / target nn.BCELoss of s_img against the domain label: the
+ *   mean over B H W of -(y max(log s, -100) + (1 - y) max(log(1 - s), -100)).
+ *   loss[1] / loss[3] = source / target BCEloss_margin: with row labels y = [domain label,
+ *   scale labels of the row's RoI] and element loss e = -(y log(s + 1e-10) + (1 - y)
+ *   log(1 - s + 1e-10)), the mean over all 4 n elements of w e, w = gate for column 0 and 1
+ *   for columns 1..3; gate (n) = e[:, 0] > 0.5 as a 0 / 1 float (written out; not
+ *   differentiated), or gate_in where given (both domains or neither; may be NULL).
+ *   Backward, from grad_loss[4] in the loss layout: dz_img = g (s - y) [s (1 - s) /
+ *   max(s (1 - s), 1e-12)] / (B H W) (0 at saturation); dz_ins = g w (-(y / (s + 1e-10) -
+ *   (1 - y) / (1 - s + 1e-10))) s (1 - s) / (4 n). */
+int tlod_us_daf_loss_f32(const float* z_img_s, const float* z_img_t, const float* z_ins_s,
+                         const float* z_ins_t, const float* rois_s, const float* rois_t,
+                         const float* gate_in_s, const float* gate_in_t, int Bs, int Bt, int Hs,
+                         int Ws, int Ht, int Wt, int n_s, int n_t, float* s_img_s,
+                         float* s_img_t, float* s_ins_s, float* s_ins_t, float* gate_s,
+                         float* gate_t, float* loss, tlod_stream_t stream);
+int tlod_us_daf_loss_bwd_f32(const float* s_img_s, const float* s_img_t, const float* s_ins_s,
+                             const float* s_ins_t, const float* rois_s, const float* rois_t,
+                             const float* gate_s, const float* gate_t, int Bs, int Bt, int Hs,
+                             int Ws, int Ht, int Wt, int n_s, int n_t, const float* grad_loss,
+                             float* dz_img_s, float* dz_img_t, float* dz_ins_s, float* dz_ins_t,
+                             tlod_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

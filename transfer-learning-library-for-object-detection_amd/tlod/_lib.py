@@ -215,6 +215,9 @@ SIGNATURES = {
     "tlod_kd_kl_bwd_f32": (c_int, [P, P, P, c_int, c_int, ctypes.c_longlong, ctypes.c_longlong,
                                    c_int, c_float, P, P, P, P]),
     "tlod_gt_cell_mask_f32": (c_int, [P, P, c_int, c_int, c_int, P, P]),
+    "tlod_roi_scale_labels_f32": (c_int, [P, c_int, P, P]),
+    "tlod_us_daf_loss_f32": (c_int, [P] * 8 + [c_int] * 8 + [P] * 8),
+    "tlod_us_daf_loss_bwd_f32": (c_int, [P] * 8 + [c_int] * 8 + [P] * 6),
 }
 
 _lib = None

@@ -128,12 +128,15 @@ DATASET_CFGS = {
                    "MAX_NUM_GT_BOXES", "20"],
     "cityscape": ["ANCHOR_SCALES", "[4,8,16,32]", "ANCHOR_RATIOS", "[0.5,1,2]",
                   "MAX_NUM_GT_BOXES", "50"],
+    # methods/US_DAF/US_DAF_train.py:219-224 (PASCAL VOC -> Clipart, 21 classes)
+    "VOC2clipart": ["ANCHOR_SCALES", "[8, 16, 32]", "ANCHOR_RATIOS", "[0.5,1,2]",
+                    "MAX_NUM_GT_BOXES", "20"],
 }
 
 
 def setup_training_cfg(net="vgg16", dataset="cityscape"):
-    """What the drivers do for --net vgg16|res101 --dataset cityscape|pascal_voc: cfgs/<net>.yml
-    then the dataset's set_cfgs."""
+    """What the drivers do for --net vgg16|res101 --dataset cityscape|pascal_voc|VOC2clipart:
+    cfgs/<net>.yml, then the dataset's set_cfgs."""
     reset_cfg()
     _merge(copy.deepcopy(VGG16_YML if net == "vgg16" else RES101_YML), cfg)
     cfg_from_list(DATASET_CFGS[dataset])
