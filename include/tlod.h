@@ -7,7 +7,13 @@
  *   - every call is stream-ordered and asynchronous on `stream` (a hipStream_t; NULL =
  *     the legacy default stream).  No entry point allocates, frees or synchronises, so a
  *     caller may capture any of them into a hipGraph;
- *   - scratch is caller-provided (`ws`, `ws_bytes`); query sizes with *_workspace_bytes;
+ *   - scratch is caller-provided (`ws`, `ws_bytes`); query sizes with *_workspace_bytes.  A
+ *     call never touches a byte past ws + its query; a query of 0 means ws may be NULL; a call
+ *     given fewer bytes than its query returns TLOD_EWORKSPACE before it launches anything
+ *     (tlod_roi_align_avg_bwd_f32 excepted: it chooses its method by ws_bytes);
+ *   - outputs need no initialisation: every element is written unless the entry point says
+ *     ACCUMULATES / ADDS (the caller zeroes or pre-fills it) or names a part as not written;
+ *     `const` inputs are never written;
  *   - return 0 on success, a negative tlod_status on failure with a message available
  *     from tlod_last_error() (thread-local).  Nothing ever calls exit() (the reference's
  *     launchers do: roi_align_kernel.cu:84-88);
@@ -105,7 +111,8 @@ int tlod_roi_align_avg_bwd_f32(const float* top_grad, int B, int C, int H, int W
  * tlod_roi_align_avg_fwd_f32's out[r][c][2i][2j]; the backward ADDS the gradient of that
  * selection into bottom_grad (B,C,H,W), deterministic (the sorted-tap gather), equal to
  * tlod_roi_align_avg_bwd_f32 of a top gradient that is zero off the selected bins.  One
- * workspace query covers both directions. */
+ * workspace query covers both directions: each of the two calls needs ws_bytes >= that query
+ * (the forward uses only its first B*H*W*C floats). */
 size_t tlod_roi_align_avg_s2_workspace_bytes(int B, int C, int H, int W, int R, int ph, int pw);
 int tlod_roi_align_avg_s2_nhwc_fwd_f32(const float* feat, int B, int C, int H, int W,
                                        const float* rois, int R, int ph, int pw, float scale,
@@ -331,7 +338,8 @@ int tlod_conv_fwd_bs_f32(const float* x, const void* wp, const float* scale, con
  * fly and nprod (6 or 3) products on the bf16 MFMA.  No weight pack.  KS = 1 or 3 (3x3 with
  * nprod = 6: the warp-specialized kernel over 4 x 16 pixel tiles, csrc/wgrad_ws.hip).  db
  * (optional, Cout floats): the bias gradient sum_{n,h,w} dy, from the staged dy rows in the
- * same launch (replaces the bias-gradient half of the ReLU backward pass). */
+ * same launch (replaces the bias-gradient half of the ReLU backward pass); accumulate != 0
+ * adds into db as it does into dw. */
 size_t tlod_conv_wgrad_bs_workspace_bytes(int N, int Cin, int H, int W, int Cout, int KS,
                                           int nprod);
 int tlod_conv_wgrad_bs_f32(const float* dy, const float* x, float* dw, float* db, int accumulate,
@@ -665,7 +673,8 @@ int tlod_image_blob_u8(const uint8_t* src, int H, int W, const float* lut, const
  * rois (R, 5) of one image, cls_prob (R, C), bbox_pred (R, 4C) (or (R, 4) when
  * class_agnostic); stds / means: 4 floats each in HOST memory; im_h, im_w: im_info[0:2].
  * R <= 2048.  dets (C, R, 5) receives, for class j, counts[j] rows (x1, y1, x2, y2, score)
- * in descending score order (ties: lower RoI index first); counts[0] = 0.  boxes_out
+ * in descending score order (ties: lower RoI index first); counts[0] = 0; what the rows past
+ * counts[j] hold is unspecified.  boxes_out
  * (R, C, 4), optional (NULL to skip): every decoded, clipped, rescaled box. */
 int tlod_detect_f32(const float* rois, const float* cls_prob, const float* bbox_pred, int R,
                     int C, int class_agnostic, const float* stds, const float* means, float im_h,

@@ -59,7 +59,9 @@ struct Carve {
     off += n * sizeof(T);
     return p;
   }
-  bool ok() const { return off <= cap; }
+  // against what the *_workspace_bytes queries report (the carved total rounded up to 256):
+  // a caller that passes less than its query is refused, whatever the padding
+  bool ok() const { return align_up(off, 256) <= cap; }
 };
 
 // Monotone float <-> uint32 map so atomicMax on uint orders floats (incl. negatives).

@@ -42,6 +42,27 @@ __device__ __forceinline__ bool before(float sa, int ia, float sb, int ib) {
   return sa > sb || (sa == sb && ia < ib);
 }
 
+// bbox_transform_inv + clip_boxes + / im_scale of RoI r for class j
+__device__ __forceinline__ float4 decode_box(const float* __restrict__ ro,
+                                             const float* __restrict__ bbox_pred, int r, int C,
+                                             int j, int agnostic, float4 stds, float4 means,
+                                             float im_h, float im_w, float im_scale) {
+  const float x1 = ro[1], y1 = ro[2], x2 = ro[3], y2 = ro[4];
+  const float* d = bbox_pred + (size_t)r * (agnostic ? 4 : 4 * C) + (agnostic ? 0 : 4 * j);
+  const float dx = d[0] * stds.x + means.x, dy = d[1] * stds.y + means.y;
+  const float dw = d[2] * stds.z + means.z, dh = d[3] * stds.w + means.w;
+  const float widths = x2 - x1 + 1.0f, heights = y2 - y1 + 1.0f;
+  const float cx = x1 + 0.5f * widths, cy = y1 + 0.5f * heights;
+  const float pcx = dx * widths + cx, pcy = dy * heights + cy;
+  const float pw = expf(dw) * widths, ph = expf(dh) * heights;
+  float4 b;
+  b.x = fminf(fmaxf(pcx - 0.5f * pw, 0.f), im_w - 1.f) / im_scale;
+  b.y = fminf(fmaxf(pcy - 0.5f * ph, 0.f), im_h - 1.f) / im_scale;
+  b.z = fminf(fmaxf(pcx + 0.5f * pw, 0.f), im_w - 1.f) / im_scale;
+  b.w = fminf(fmaxf(pcy + 0.5f * ph, 0.f), im_h - 1.f) / im_scale;
+  return b;
+}
+
 __global__ void __launch_bounds__(kThreads) detect_kernel(
     const float* __restrict__ rois, const float* __restrict__ cls_prob,
     const float* __restrict__ bbox_pred, int R, int C, int agnostic, float im_h, float im_w,
@@ -57,21 +78,17 @@ __global__ void __launch_bounds__(kThreads) detect_kernel(
   if (t == 0) n_cand = 0;
   // 1. decode / clip / rescale every RoI for class j; candidates score > thresh
   for (int r = t; r < R; r += kThreads) {
-    const float* ro = rois + (size_t)r * 5;
-    const float x1 = ro[1], y1 = ro[2], x2 = ro[3], y2 = ro[4];
-    const float* d = bbox_pred + (size_t)r * (agnostic ? 4 : 4 * C) + (agnostic ? 0 : 4 * j);
-    const float dx = d[0] * stds.x + means.x, dy = d[1] * stds.y + means.y;
-    const float dw = d[2] * stds.z + means.z, dh = d[3] * stds.w + means.w;
-    const float widths = x2 - x1 + 1.0f, heights = y2 - y1 + 1.0f;
-    const float cx = x1 + 0.5f * widths, cy = y1 + 0.5f * heights;
-    const float pcx = dx * widths + cx, pcy = dy * heights + cy;
-    const float pw = expf(dw) * widths, ph = expf(dh) * heights;
-    float4 b;
-    b.x = fminf(fmaxf(pcx - 0.5f * pw, 0.f), im_w - 1.f) / im_scale;
-    b.y = fminf(fmaxf(pcy - 0.5f * ph, 0.f), im_h - 1.f) / im_scale;
-    b.z = fminf(fmaxf(pcx + 0.5f * pw, 0.f), im_w - 1.f) / im_scale;
-    b.w = fminf(fmaxf(pcy + 0.5f * ph, 0.f), im_h - 1.f) / im_scale;
-    if (boxes_out) reinterpret_cast<float4*>(boxes_out)[(size_t)r * C + j] = b;
+    const float4 b = decode_box(rois + (size_t)r * 5, bbox_pred, r, C, j, agnostic, stds, means,
+                                im_h, im_w, im_scale);
+    if (boxes_out) {
+      reinterpret_cast<float4*>(boxes_out)[(size_t)r * C + j] = b;
+      // the background column has no workgroup of its own: class 1's writes it, so that
+      // boxes_out is written in full
+      if (j == 1)
+        reinterpret_cast<float4*>(boxes_out)[(size_t)r * C] =
+            decode_box(rois + (size_t)r * 5, bbox_pred, r, C, 0, agnostic, stds, means, im_h,
+                       im_w, im_scale);
+    }
     box[r] = b;
   }
   __syncthreads();

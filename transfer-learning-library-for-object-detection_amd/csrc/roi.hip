@@ -884,7 +884,9 @@ extern "C" int tlod_roi_align_avg_s2_nhwc_fwd_f32(const float* feat, int B, int 
   TLOD_CHECK_ARG(B > 0 && C > 0 && H >= 2 && W >= 2 && R >= 0, "bad shape");
   TLOD_CHECK_ARG(ph >= 1 && pw >= 1 && ph <= 7 && pw <= 7, "fused RoIAlignAvg supports 1..7 bins");
   if (R == 0) return kOk;
-  if (ws == nullptr || ws_bytes < (size_t)B * H * W * C * sizeof(float)) {
+  // one query for both directions (include/tlod.h): the forward's own need, the channels-last
+  // map, is the smaller part of it
+  if (ws == nullptr || ws_bytes < tlod_roi_align_avg_s2_workspace_bytes(B, C, H, W, R, ph, pw)) {
     set_error("tlod_roi_align_avg_s2_nhwc_fwd_f32: workspace too small");
     return kWorkspace;
   }

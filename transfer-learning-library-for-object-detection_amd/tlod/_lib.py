@@ -289,9 +289,45 @@ def workspace(nbytes, device, name):
     """Grow-only scratch buffer per (op name, device, stream) for the C ABI's
     caller-provided workspace.  Distinct names keep two-phase ops (anchor target,
     proposal target) from sharing scratch with ops launched between their phases."""
+    if env("TLOD_WS_GUARD", "0") != "0":
+        return _guarded_workspace(nbytes, device, name)
     key = (name, str(device), _raw_stream(_dev_index(device)))
     buf = _ws_cache.get(key)
     if buf is None or buf.numel() < nbytes:
         buf = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
         _ws_cache[key] = buf
     return buf
+
+
+# TLOD_WS_GUARD=1 (a test mode): no cache — every call gets a view of exactly the queried
+# length inside a fresh buffer with canaries on both sides, so a kernel runs with the
+# workspace its *_workspace_bytes query promised and a store past it is seen.
+WS_CANARY_BYTES = 64 << 10
+WS_CANARY = 0xC7
+_ws_guarded = []  # (op name, whole buffer, view length), until check_workspace_guards()
+
+
+def _guarded_workspace(nbytes, device, name):
+    n = max(int(nbytes), 256)
+    buf = torch.full((2 * WS_CANARY_BYTES + n,), WS_CANARY, dtype=torch.uint8, device=device)
+    _ws_guarded.append((name, buf, n))
+    return buf[WS_CANARY_BYTES:WS_CANARY_BYTES + n]
+
+
+def check_workspace_guards():
+    """Synchronise, verify the canaries of every workspace handed out under TLOD_WS_GUARD
+    since the last check (RuntimeError naming the op on damage) and forget the buffers.
+    Returns how many were checked."""
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()
+    held, bad = list(_ws_guarded), []
+    del _ws_guarded[:]
+    for name, buf, n in held:
+        front = buf[:WS_CANARY_BYTES] != WS_CANARY
+        back = buf[WS_CANARY_BYTES + n:] != WS_CANARY
+        nf, nb = int(front.sum()), int(back.sum())
+        if nf or nb:
+            bad.append(f"{name} ({n} B): {nf} bytes before, {nb} bytes past the workspace")
+    if bad:
+        raise RuntimeError("workspace canaries damaged: " + "; ".join(bad))
+    return len(held)

@@ -17,7 +17,9 @@ from ..config import cfg
 def detect(rois, cls_prob, bbox_pred, im_info, class_agnostic=False, thresh=0.0, nms=None,
            return_boxes=False):
     """One image: rois (R, 5), cls_prob (R, C), bbox_pred (R, 4C | 4), im_info (3,) device
-    tensors -> (dets (C, R, 5), counts (C,) int32[, boxes (R, C, 4)]) on the device."""
+    tensors -> (dets (C, R, 5), counts (C,) int32[, boxes (R, C, 4)]) on the device.  boxes
+    holds the decoded box of every class, the background column boxes[:, 0] included (it used
+    to come back as zeros); rows of dets past counts[j] are unspecified."""
     _lib.require_cuda(rois, cls_prob, bbox_pred)
     rois = rois.detach().reshape(-1, 5).contiguous().float()
     cls_prob = cls_prob.detach().reshape(rois.shape[0], -1).contiguous().float()
@@ -31,8 +33,8 @@ def detect(rois, cls_prob, bbox_pred, im_info, class_agnostic=False, thresh=0.0,
              if cfg.TRAIN.BBOX_NORMALIZE_TARGETS_PRECOMPUTED else ctypes_floats((0, 0, 0, 0)))
     dets = torch.empty((C, R, 5), dtype=torch.float32, device=rois.device)
     counts = torch.empty(C, dtype=torch.int32, device=rois.device)
-    boxes = torch.zeros((R, C, 4), dtype=torch.float32, device=rois.device) if return_boxes \
-        else None
+    boxes = torch.empty((R, C, 4), dtype=torch.float32, device=rois.device) if return_boxes \
+        else None  # written in full, the background column included
     _lib.check(_lib.lib().tlod_detect_f32(
         _lib.ptr(rois), _lib.ptr(cls_prob), _lib.ptr(bbox_pred), R, C, int(class_agnostic), stds,
         means, info[0], info[1], info[2], float(thresh),
