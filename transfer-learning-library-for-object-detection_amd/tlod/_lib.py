@@ -220,6 +220,21 @@ SIGNATURES = {
     "tlod_us_daf_loss_bwd_f32": (c_int, [P] * 8 + [c_int] * 8 + [P] * 6),
 }
 
+# include/tlod_idf.h: the IDF extension of the ABI, bound by lib() like SIGNATURES (its own
+# table and header, so the main header's ledger stays what it is)
+EXT_SIGNATURES = {
+    "tlod_idf_dam_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "tlod_idf_dam_f32": (c_int, [P, c_int, c_int, c_int, c_int, P, P, c_size_t, P]),
+    "tlod_idf_sep_fwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "tlod_idf_sep_fwd_f32": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P,
+                                     c_size_t, P]),
+    "tlod_idf_sep_bwd_f32": (c_int, [P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P, P,
+                                     P]),
+    "tlod_idf_domain_loss_f32": (c_int, [P, c_int, c_int, P, c_int, c_int, c_float, P, P]),
+    "tlod_idf_domain_loss_bwd_f32": (c_int, [P, c_int, c_int, P, c_int, c_int, c_float, P, P, P,
+                                             P]),
+}
+
 _lib = None
 
 
@@ -232,7 +247,7 @@ def lib():
                 f"libtlod.so not found at {LIB_PATH}: build it with "
                 "`python -c 'import __graft_entry__ as g; g.build()'` (no CPU fallback exists)")
         L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
             if os.environ.get("TLOD_LIB") and not hasattr(L, name):
                 continue  # an older tuning build (A/B timing) may predate an entry point
             fn = getattr(L, name)

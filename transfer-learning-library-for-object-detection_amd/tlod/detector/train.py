@@ -16,7 +16,7 @@ from ..config import cfg, setup_training_cfg
 from ..data.imdb import CITYSCAPE_CLASSES as CITYSCAPES_CLASSES  # cityscape.py:51-54
 
 
-METHODS = ("faster_rcnn", "daf", "maf", "atf", "pt_maf", "us_daf")
+METHODS = ("faster_rcnn", "daf", "maf", "atf", "pt_maf", "us_daf", "idf")
 
 
 def build_model(method, device, net="vgg16", classes=CITYSCAPES_CLASSES, seed=0,
@@ -105,10 +105,12 @@ class SyntheticCityscapes:
     """Synthetic batches of the reference's input tensors:
     BGR uint8 uniform[0,255] at 600x1200 minus PIXEL_MEANS (NCHW fp32); source gt = 8
     boxes (x1 in [0,W-64), size 32..400, clipped, class 1..8) padded to 50;
-    target gt = [1,1,1,1,1] (roibatchLoader.py:217-226).  A small pool of batches is made
-    resident on the device up front so the timed loop reads HBM only."""
+    target gt = [1,1,1,1,1] (roibatchLoader.py:217-226), or with tgt_G > 0 that many
+    source-style boxes (IDF's pseudo labels).  A small pool of batches is made resident on the
+    device up front so the timed loop reads HBM only."""
 
-    def __init__(self, device, H=600, W=1200, G=8, max_gt=50, pool=4, seed=1000, n_classes=8):
+    def __init__(self, device, H=600, W=1200, G=8, max_gt=50, pool=4, seed=1000, n_classes=8,
+                 tgt_G=0):
         self.device = torch.device(device)
         rng = np.random.default_rng(seed)
         means = torch.tensor(cfg.PIXEL_MEANS.reshape(3), dtype=torch.float32)
@@ -117,23 +119,32 @@ class SyntheticCityscapes:
             def img():
                 u8 = torch.from_numpy(rng.integers(0, 256, (H, W, 3), dtype=np.uint8))
                 return (u8.float() - means).permute(2, 0, 1).contiguous()[None]
-            gt = np.zeros((1, max_gt, 5), np.float32)
-            x1 = rng.uniform(0, W - 64, G)
-            y1 = rng.uniform(0, H - 64, G)
-            w = rng.uniform(32, 400, G)
-            h = rng.uniform(32, 400, G)
-            gt[0, :G, 0] = x1
-            gt[0, :G, 1] = y1
-            gt[0, :G, 2] = np.minimum(x1 + w, W - 1)
-            gt[0, :G, 3] = np.minimum(y1 + h, H - 1)
-            gt[0, :G, 4] = rng.integers(1, n_classes + 1, G)
+            def boxes(n):
+                gt = np.zeros((1, max_gt, 5), np.float32)
+                x1 = rng.uniform(0, W - 64, n)
+                y1 = rng.uniform(0, H - 64, n)
+                w = rng.uniform(32, 400, n)
+                h = rng.uniform(32, 400, n)
+                gt[0, :n, 0] = x1
+                gt[0, :n, 1] = y1
+                gt[0, :n, 2] = np.minimum(x1 + w, W - 1)
+                gt[0, :n, 3] = np.minimum(y1 + h, H - 1)
+                gt[0, :n, 4] = rng.integers(1, n_classes + 1, n)
+                return torch.from_numpy(gt)
+            gt = boxes(G)
             info = torch.tensor([[H, W, 600.0 / 1024.0]], dtype=torch.float32)
             d = self.device
-            self.batches.append((
-                img().to(d), info.to(d), torch.from_numpy(gt).to(d),
-                torch.tensor([G], dtype=torch.int64, device=d), torch.ones(1, device=d),
-                img().to(d), info.clone().to(d), torch.ones((1, 5), device=d),
-                torch.zeros(1, dtype=torch.int64, device=d), torch.zeros(1, device=d)))
+            src = (img().to(d), info.to(d), gt.to(d),
+                   torch.tensor([G], dtype=torch.int64, device=d), torch.ones(1, device=d))
+            tgt_img = img().to(d)
+            if tgt_G > 0:  # drawn after everything the default batch draws
+                tgt_gt = boxes(tgt_G).to(d)
+                tgt_num = torch.tensor([tgt_G], dtype=torch.int64, device=d)
+            else:
+                tgt_gt = torch.ones((1, 5), device=d)
+                tgt_num = torch.zeros(1, dtype=torch.int64, device=d)
+            self.batches.append(src + (tgt_img, info.clone().to(d), tgt_gt, tgt_num,
+                                       torch.zeros(1, device=d)))
         self.i = 0
 
     def next(self):
@@ -148,6 +159,11 @@ def daf_loss(out, lamda=0.1):
 
 
 def default_clip(model):
+    """clip_gradient's norm: 10 for VGG16, none for ResNet101 (DAF_train.py:406-407); a model
+    with its own ``clip_norm`` (IDF: 0, its training script never clips) says so."""
+    own = getattr(model, "clip_norm", None)
+    if own is not None:
+        return float(own)
     return 10.0 if getattr(model, "net", "vgg16") == "vgg16" else 0.0
 
 
@@ -194,6 +210,47 @@ def pt_maf_train_step(model, teacher, optimizer, batch, lamda=0.1, T=3.0, high=0
     out = model(*batch, T=T, high=high, low=low, alpha=alpha, beta=beta, gamma=gamma)
     teacher_out = kd_teacher(teacher, batch[0], batch[1], batch[2], batch[3], out[0], T)
     loss = model.total_loss(out, lamda, kd_loss(model, teacher_out, out[7], T))
+    loss.backward()
+    scale = 1.0
+    if reducer is not None:
+        reducer.finish(scale=not fused)
+        scale = reducer.grad_scale
+    if fused:
+        optimizer.step(grad_scale=scale)
+    else:
+        clip = default_clip(model)
+        if clip:
+            clip_gradient_([p for p in model.parameters()], clip)
+        optimizer.step()
+    return loss.detach()
+
+
+def idf_forward(model, batch, separation=True, eta=1.0):
+    """The two calls of an IDF iteration over the project's 10-tuple batch: the source image
+    with its ground truth (IDF_train.py:228), then the target image with ``target=True``, the
+    batch's target gt_boxes / num_boxes as the pseudo boxes and the reference's single all-zero
+    box for the main stack (:277-286).  Returns (out_s, out_t), the model's 20-tuples."""
+    im, info, gt, num, _, t_im, t_info, t_gt, t_num, _ = batch
+    out_s = model(im, info, gt, num, gt, num, separation, False, eta)
+    out_t = model(t_im, t_info, t_gt.new_zeros((1, 1, 5)), t_num.new_zeros(1),
+                  t_gt.view(1, -1, 5), t_num, separation, True, eta)
+    return out_s, out_t
+
+
+def idf_train_step(model, optimizer, batch, separation=True, gamma=3.0, eta=1.0, reducer=None):
+    """One IDF iteration (methods/IDF/IDF_train.py:223-339) over the project's 10-tuple batch:
+    the source call on the ground truth, the target call (``target=True``) with the batch's
+    target gt_boxes / num_boxes as the pseudo boxes and the reference's single all-zero box
+    for the main stack (:277-280), the loss sum (model.total_loss), backward, update.  No
+    gradient clipping.  Returns the loss as a device tensor (no host sync)."""
+    from ..optim import FusedClipOptimizer
+    fused = isinstance(optimizer, FusedClipOptimizer)
+    if reducer is not None:
+        reducer.zero_grad()
+    else:
+        optimizer.zero_grad(set_to_none=True)
+    out_s, out_t = idf_forward(model, batch, separation, eta)
+    loss = model.total_loss(out_s, out_t, separation, gamma)
     loss.backward()
     scale = 1.0
     if reducer is not None:
