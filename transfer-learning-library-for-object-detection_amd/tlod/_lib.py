@@ -235,6 +235,27 @@ EXT_SIGNATURES = {
                                              P]),
 }
 
+# include/tlod_pa_atf.h: the PA-ATF extension (strided conv im2col / col2im, channel gate,
+# prototype pooling), a third table with its own header and ledger (tests/test_pa_atf_cpu.py)
+PA_ATF_SIGNATURES = {
+    "tlod_im2col_f32": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
+    "tlod_col2im_f32": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
+    "tlod_pa_gate_f32": (c_int, [P, c_int, c_int, c_int, c_int, P, P, P]),
+    "tlod_pa_gate_bwd_f32": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P, P]),
+    "tlod_pa_proto_pool_fwd_f32": (c_int, [P, c_int, c_int, c_int, P, c_int, c_float, P, P, P, P,
+                                           P, P]),
+    "tlod_pa_proto_pool_bwd_f32": (c_int, [P, P, P, P, P, P, c_int, c_float, c_int, c_int, c_int,
+                                           c_float, P, P]),
+    "tlod_pa_atf_loss_f32": (c_int, [P, P, P, P, P]),
+    "tlod_pa_atf_loss_bwd_f32": (c_int, [P, P, P, P, P, P]),
+    "tlod_proposal_keep_f32": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int,
+                                       c_float, P, P, P, c_size_t, P]),
+    "tlod_proposal_pick_f32": (c_int, [P, P, c_int, c_int, c_int, c_int, P, P, c_uint64, P, P]),
+    "tlod_proposal_subsample_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "tlod_proposal_subsample_f32": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int,
+                                            c_int, c_int, c_float, c_uint64, P, P, c_size_t, P]),
+}
+
 _lib = None
 
 
@@ -247,7 +268,8 @@ def lib():
                 f"libtlod.so not found at {LIB_PATH}: build it with "
                 "`python -c 'import __graft_entry__ as g; g.build()'` (no CPU fallback exists)")
         L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
+        for name, (res, args) in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items())
+                                  + list(PA_ATF_SIGNATURES.items())):
             if os.environ.get("TLOD_LIB") and not hasattr(L, name):
                 continue  # an older tuning build (A/B timing) may predate an entry point
             fn = getattr(L, name)

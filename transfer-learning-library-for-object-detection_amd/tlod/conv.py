@@ -743,3 +743,129 @@ def vgg_init_(conv):
     conv.weight.data.normal_(0, math.sqrt(2.0 / n))
     if conv.bias is not None:
         conv.bias.data.zero_()
+
+
+# ---------------------------------------------------------------------- strided convolution
+def sconv_on():
+    """TLOD_SCONV (default 1): StridedConv2d on libtlod (im2col + split-bf16 GEMM + col2im);
+    0 = F.conv2d."""
+    return _lib.env("TLOD_SCONV", "1") != "0"
+
+
+def conv_out_size(H, W, KS, stride, pad):
+    return (H + 2 * pad - KS) // stride + 1, (W + 2 * pad - KS) // stride + 1
+
+
+def im2col(x, KS, stride, pad):
+    """col (N Ho Wo, C KS KS) of a contiguous NCHW map (tlod_im2col_f32): row (n, ho, wo),
+    column (c, kh, kw) — F.unfold's values, transposed to pixel-major rows."""
+    _lib.require_cuda(x)
+    x = x.contiguous()
+    N, C, H, W = x.shape
+    Ho, Wo = conv_out_size(H, W, KS, stride, pad)
+    col = torch.empty((max(N * Ho * Wo, 0), C * KS * KS), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().tlod_im2col_f32(_lib.ptr(x), N, C, H, W, KS, stride, pad, _lib.ptr(col),
+                                          _lib.stream_of(x)), "im2col")
+    return col
+
+
+def col2im(dcol, shape, KS, stride, pad):
+    """The adjoint of im2col: dx of `shape` (N, C, H, W), fully written (tlod_col2im_f32)."""
+    _lib.require_cuda(dcol)
+    dcol = dcol.contiguous()
+    N, C, H, W = shape
+    dx = torch.empty(shape, dtype=torch.float32, device=dcol.device)
+    _lib.check(_lib.lib().tlod_col2im_f32(_lib.ptr(dcol), N, C, H, W, KS, stride, pad,
+                                          _lib.ptr(dx), _lib.stream_of(dcol)), "col2im")
+    return dx
+
+
+class StridedConvFunction(torch.autograd.Function):
+    """y = act(conv2d(x, weight, bias, stride, padding)) as three split-bf16 GEMMs (nprod 6:
+    f32-level error) around tlod_im2col_f32 / tlod_col2im_f32.
+
+    The result is logically NCHW, as F.conv2d's, and channels-last in memory: it is a
+    permuted view of the GEMM's (N Ho Wo, Cout) rows (a consumer that needs NCHW memory calls
+    .contiguous(); a gradient that arrives channels-last is read without a copy).
+    col, (N Ho Wo, Cin KS^2) floats — 124 MB for the conv3-level Convm1 of a 600 x 1200 PA-ATF
+    step — is not held through the step: the backward recomputes it for the weight gradient."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride, pad, relu, tap=None):
+        from .linear import gemm
+        N, C, H, W = x.shape
+        Cout, KS = weight.shape[0], weight.shape[2]
+        Ho, Wo = conv_out_size(H, W, KS, stride, pad)
+        M, K = N * Ho * Wo, C * KS * KS
+        if max(M, Cout, K) * max(M, K) * 4 >= 1 << 31:
+            raise NotImplementedError("StridedConv2d: an im2col matrix of 2 GiB or more")
+        x = x.contiguous()
+        col = im2col(x, KS, stride, pad)
+        y2 = gemm(col, weight.detach().view(Cout, K), M, Cout, K, 1, 1, bias, relu=bool(relu))
+        del col
+        y = y2.view(N, Ho, Wo, Cout).permute(0, 3, 1, 2)
+        if tap is not None:  # test instrumentation (StridedConv2d.act_tap): the activation
+            tap.append(y.detach().clone())
+        ctx.geo = (N, C, H, W, Cout, KS, stride, pad, Ho, Wo)
+        ctx.relu, ctx.has_bias = bool(relu), bias is not None
+        ctx.params = (weight, bias)  # gradient slots (tlod.grads)
+        ctx.save_for_backward(x, weight, y2 if relu else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        from .linear import gemm
+        x, weight, y2 = ctx.saved_tensors
+        N, C, H, W, Cout, KS, stride, pad, Ho, Wo = ctx.geo
+        M, K = N * Ho * Wo, C * KS * KS
+        g = dy.permute(0, 2, 3, 1).reshape(M, Cout)  # no copy for a channels-last gradient
+        if ctx.relu:
+            g = torch.where(y2 > 0, g, torch.zeros((), dtype=g.dtype, device=g.device))
+        g = g.contiguous()
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:  # dcol = g W, then the gather
+            dcol = gemm(g, weight.detach().view(Cout, K), M, K, Cout, 1, 0)
+            dx = col2im(dcol, (N, C, H, W), KS, stride, pad)
+            del dcol
+        if ctx.needs_input_grad[1]:  # dW = g^T col: both operands M/N-contiguous
+            col = im2col(x, KS, stride, pad)
+            slot = grad_out(ctx.params[0])
+            dw = gemm(g, col, Cout, K, M, 0, 0, out=slot.view(Cout, K) if slot is not None else None)
+            dw = slot if slot is not None else dw.view_as(weight)
+        if ctx.has_bias and ctx.needs_input_grad[2]:
+            slot = grad_out(ctx.params[1])
+            db = g.sum(0) if slot is None else torch.sum(g, 0, out=slot)
+        return dx, dw, db, None, None, None, None
+
+
+class StridedConv2d(nn.Conv2d):
+    """nn.Conv2d-compatible (same parameters, state_dict keys and default init) for square
+    kernels with any stride >= 1 and padding >= 0, on libtlod; optional fused ReLU.  PA-ATF's
+    mask nets (5x5 stride 3, 3x3 stride 2) and CLUB's first conv (3x3 stride 2).  Returns what
+    F.conv2d returns, logically NCHW in channels-last memory (StridedConvFunction).
+    TLOD_SCONV=0: F.conv2d (+ ReLU)."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, bias=True,
+                 relu=False):
+        k = kernel_size if isinstance(kernel_size, int) else kernel_size[0]
+        if not isinstance(kernel_size, int) and kernel_size[0] != kernel_size[1]:
+            raise NotImplementedError("tlod.StridedConv2d: square kernels only")
+        if not (isinstance(stride, int) and isinstance(padding, int) and stride >= 1
+                and padding >= 0):
+            raise NotImplementedError("tlod.StridedConv2d: one int stride >= 1 and padding >= 0")
+        super().__init__(in_channels, out_channels, k, stride=stride, padding=padding, bias=bias)
+        self.relu = relu
+        self.act_tap = None  # tests: a list receiving each forward's activation
+
+    def forward(self, x):
+        if not sconv_on():
+            y = F.conv2d(x, self.weight, self.bias, self.stride, self.padding)
+            y = F.relu(y) if self.relu else y
+            if self.act_tap is not None:
+                self.act_tap.append(y.detach().clone())
+            return y
+        return StridedConvFunction.apply(x, self.weight, self.bias, self.stride[0],
+                                         self.padding[0], self.relu, self.act_tap)
+
+    def extra_repr(self):
+        return super().extra_repr() + (", relu=True" if self.relu else "")

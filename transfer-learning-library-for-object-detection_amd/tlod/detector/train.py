@@ -16,7 +16,7 @@ from ..config import cfg, setup_training_cfg
 from ..data.imdb import CITYSCAPE_CLASSES as CITYSCAPES_CLASSES  # cityscape.py:51-54
 
 
-METHODS = ("faster_rcnn", "daf", "maf", "atf", "pt_maf", "us_daf", "idf")
+METHODS = ("faster_rcnn", "daf", "maf", "atf", "pt_maf", "us_daf", "idf", "pa_atf")
 
 
 def build_model(method, device, net="vgg16", classes=CITYSCAPES_CLASSES, seed=0,
