@@ -7,6 +7,14 @@ CPU restatement (oracle/), whose anchor generator is pinned by the reference's o
 known-answer table (generate_anchors.py:29-37).  The fixtures freeze the restatement so
 both the oracle (tests/test_golden.py, CPU) and the HIP path (GPU) are checked against
 the same vectors; recorded numpy draws let the HIP targets replay the sampling.
+
+These vectors come from the restatement, so they cannot show that the restatement reads the
+reference correctly.  reference_v1.npz (make_reference_golden.py, tests/test_reference_golden.py)
+does that for the layers the reference can run on a CPU: the anchor table, the anchor-target,
+proposal-target and proposal layers (PA-ATF's subsampled form included), the box primitives,
+smooth-L1, the affine theta / grid, clip_gradient, MAF's DRM and US-DAF's image head.  What
+this file holds beyond those is restatement only: NMS, the RoIAlign / RoIPool kernels (and,
+elsewhere in the suite, RoICrop, the image blob and the per-method loss graphs).
 """
 import os
 import sys
