@@ -128,7 +128,9 @@ int tlod_roi_align_avg_s2_nhwc_bwd_f32(const float* top_grad, int B, int C, int 
  *   lib/model/roi_pooling/src/roi_pooling_cuda.c (kernels roi_pooling_kernel.cu:24-203).
  * argmax: int32 (R,C,ph,pw), flat index into feat or -1 for an empty bin.
  * bwd ACCUMULATES into bottom_grad (zero it first); it scatters through argmax
- * (equal sums to the reference's O(B*C*H*W*R) gather). */
+ * (equal sums to the reference's O(B*C*H*W*R) gather, except for RoIs whose rounded extent
+ * is inverted: see tlod_roi_pool_bwd_gather_f32 in tlod_roi.h, which applies the gather's
+ * own tests). */
 int tlod_roi_pool_fwd_f32(const float* feat, int B, int C, int H, int W,
                           const float* rois, int R, int ph, int pw, float scale,
                           float* out, int32_t* argmax, tlod_stream_t stream);

@@ -38,6 +38,23 @@ def test_ctypes_table_matches_header():
     assert sorted(_lib.SIGNATURES) == declared_symbols()
 
 
+def test_roi_extension_header_matches_its_table():
+    """include/tlod_roi.h == tlod._lib.ROI_SIGNATURES, disjoint from the other tables, every
+    name exported, and each has a guard-band case in tests/test_abi_guard_gpu.py."""
+    from tlod import _lib
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "tlod_roi.h")).read(),
+                 flags=re.S)
+    syms = sorted(set(re.findall(r"\b(tlod_[a-z0-9_]+)\s*\(", src)))
+    assert syms and sorted(_lib.ROI_SIGNATURES) == syms
+    for other in (_lib.SIGNATURES, _lib.EXT_SIGNATURES, _lib.PA_ATF_SIGNATURES):
+        assert not set(syms) & set(other)
+    L = ctypes.CDLL(_lib.LIB_PATH)
+    assert all(hasattr(L, s) for s in syms)
+    guard = open(os.path.join(ROOT, "tests", "test_abi_guard_gpu.py")).read()
+    for s in syms:
+        assert re.search(r"\.run\(\s*L\." + s + r"\b", guard), s
+
+
 def test_host_only_calls():
     from tlod import _lib
     L = _lib.lib()

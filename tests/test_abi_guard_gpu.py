@@ -1002,6 +1002,31 @@ def test_roi_pool_fwd_bwd():
     guard_case(bwd, lambda o: _acc_np(o, P, ref))
 
 
+def test_roi_pool_bwd_gather_accumulates():
+    """include/tlod_roi.h: the backward with the reference gather's tests.  Two RoIs are
+    replaced by ones whose rounded extent is inverted; the oracle passes no gradient there."""
+    feat, rois, P = roi_data()
+    rois = rois.copy()
+    rois[0, 1:] = [16 * 6.0, 16 * 4.0, 16 * 2.0, 16 * 1.0]
+    rois[1, 1:] = [16 * 5.0, 16 * 1.0, 16 * 1.0, 16 * 3.0]
+    L, t = lib(), torch.from_numpy
+    ro, ra = oroi.roi_pool_fwd(feat, rois, 7, 7, SCALE)
+    assert (ra[:2] >= 0).all()
+    g = np.random.default_rng(7).standard_normal(ro.shape).astype(np.float32)
+    ref = oroi.roi_pool_bwd(g, ra, rois, RB, RC, RH, RW, SCALE)
+    g0 = g.copy()
+    g0[:2] = 0
+    np.testing.assert_array_equal(ref, oroi.roi_pool_bwd(g0, ra, rois, RB, RC, RH, RW, SCALE))
+
+    def bwd(c, over):
+        bg = c.acc(t(P), "bottom_grad")
+        st = c.run(L.tlod_roi_pool_bwd_gather_f32, c.inp(t(g), "top_grad"),
+                   c.inp(t(np.ascontiguousarray(ra, np.int32)), "argmax"), RB, RC, RH, RW,
+                   c.inp(t(rois), "rois"), RR, 7, 7, SCALE, bg)
+        return st, 0, bg
+    guard_case(bwd, lambda o: _acc_np(o, P, ref))
+
+
 @pytest.mark.parametrize("tier", ["gather", "accumulator", "null"])
 def test_roi_align_avg_bwd_tiers(tier):
     """The three tiers are chosen by ws_bytes, so there is no too-small case here."""

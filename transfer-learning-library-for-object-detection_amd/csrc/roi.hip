@@ -11,7 +11,8 @@
 //     contiguous, coalesced slab (the reference writes the 8x8 map to HBM, then a
 //     second torch kernel re-reads it).  Backward fuses avg_pool2d's backward.
 //   * RoIPool backward scatters through argmax (O(R*C*ph*pw) atomics) instead of the
-//     reference's O(B*C*H*W*R) gather (roi_pooling_kernel.cu:128-203).
+//     reference's O(B*C*H*W*R) gather (roi_pooling_kernel.cu:128-203); the *_gather entry
+//     point (tlod_roi.h) applies the gather's own membership tests to each bin.
 #include <algorithm>
 #include <cfloat>
 
@@ -19,6 +20,7 @@
 
 #include "common.h"
 #include "tlod.h"
+#include "tlod_roi.h"
 
 namespace tlod {
 
@@ -712,6 +714,7 @@ __global__ void roi_pool_fwd_kernel(int total, const float* __restrict__ feat, f
   }
 }
 
+// The plain scatter through argmax (tlod_roi_pool_bwd_f32).
 __global__ void roi_pool_bwd_kernel(int total, const float* __restrict__ top,
                                     const int32_t* __restrict__ argmax,
                                     float* __restrict__ grad) {
@@ -719,6 +722,47 @@ __global__ void roi_pool_bwd_kernel(int total, const float* __restrict__ top,
        index += blockDim.x * gridDim.x) {
     const int a = argmax[index];
     if (a >= 0) atomicAdd(grad + a, top[index]);
+  }
+}
+
+// The reference's backward is a gather per input element (roi_pooling_kernel.cu:128-203): it
+// adds top_diff(roi, c, ph, pw) to element a of channel c only if a is that bin's argmax, a's
+// image is the RoI's (:150-154), (h, w) lies inside the rounded, unclipped, inclusive RoI
+// extent (:162-166) and (ph, pw) lies in the feasible bin range of (h, w) (:182-190).  This
+// scatter applies the same tests per bin (tlod_roi_pool_bwd_gather_f32), so a RoI whose
+// rounded extent is inverted (forced to 1 x 1 by the forward, which pools the cell at its
+// start) passes no gradient, as in the reference.
+// Batch indices are assumed integral: (int)r[0] truncates a fractional one as the reference's
+// int conversion does, here and in the forward.
+__global__ void roi_pool_bwd_gather_kernel(int total, const float* __restrict__ top,
+                                           const int32_t* __restrict__ argmax, float scale,
+                                           int n_in, int C, int H, int W, int PH, int PW,
+                                           const float* __restrict__ rois,
+                                           float* __restrict__ grad) {
+  for (int index = blockIdx.x * blockDim.x + threadIdx.x; index < total;
+       index += blockDim.x * gridDim.x) {
+    const int a = argmax[index];
+    if (a < 0 || a >= n_in) continue;
+    const int pw = index % PW;
+    const int ph = (index / PW) % PH;
+    const int c = (index / PW / PH) % C;
+    const int n = index / PW / PH / C;
+    const float* r = rois + n * 5;
+    const int w = a % W, h = (a / W) % H, ch = (a / W / H) % C, img = a / W / H / C;
+    if (img != (int)r[0] || ch != c) continue;
+    const int sw = (int)round(r[1] * scale), sh = (int)round(r[2] * scale);
+    const int ew = (int)round(r[3] * scale), eh = (int)round(r[4] * scale);
+    if (!(w >= sw && w <= ew && h >= sh && h <= eh)) continue;
+    const int rw = max(ew - sw + 1, 1), rh = max(eh - sh + 1, 1);
+    const float bh = (float)rh / (float)PH, bw = (float)rw / (float)PW;
+    int phs = (int)floorf((float)(h - sh) / bh), phe = (int)ceilf((float)(h - sh + 1) / bh);
+    int pws = (int)floorf((float)(w - sw) / bw), pwe = (int)ceilf((float)(w - sw + 1) / bw);
+    phs = min(max(phs, 0), PH);
+    phe = min(max(phe, 0), PH);
+    pws = min(max(pws, 0), PW);
+    pwe = min(max(pwe, 0), PW);
+    if (ph < phs || ph >= phe || pw < pws || pw >= pwe) continue;
+    atomicAdd(grad + a, top[index]);
   }
 }
 
@@ -979,6 +1023,21 @@ extern "C" int tlod_roi_pool_bwd_f32(const float* top_grad, const int32_t* argma
   if (total == 0) return kOk;
   hipLaunchKernelGGL(roi_pool_bwd_kernel, dim3(grid_for(total, 256)), dim3(256), 0,
                      (hipStream_t)stream, total, top_grad, argmax, bottom_grad);
+  TLOD_LAUNCH_CHECK();
+  return kOk;
+}
+
+extern "C" int tlod_roi_pool_bwd_gather_f32(const float* top_grad, const int32_t* argmax, int B,
+                                            int C, int H, int W, const float* rois, int R, int ph,
+                                            int pw, float scale, float* bottom_grad,
+                                            tlod_stream_t stream) {
+  TLOD_CHECK_ARG(B > 0 && C > 0 && H > 0 && W > 0 && R >= 0 && ph > 0 && pw > 0, "bad shape");
+  TLOD_CHECK_ARG((size_t)B * C * H * W < (1ull << 31), "feature map too large for int32 argmax");
+  const int total = R * C * ph * pw;
+  if (total == 0) return kOk;
+  hipLaunchKernelGGL(roi_pool_bwd_gather_kernel, dim3(grid_for(total, 256)), dim3(256), 0,
+                     (hipStream_t)stream, total, top_grad, argmax, scale, B * C * H * W, C, H, W,
+                     ph, pw, rois, bottom_grad);
   TLOD_LAUNCH_CHECK();
   return kOk;
 }

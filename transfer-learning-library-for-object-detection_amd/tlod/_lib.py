@@ -256,6 +256,14 @@ PA_ATF_SIGNATURES = {
                                             c_int, c_int, c_float, c_uint64, P, P, c_size_t, P]),
 }
 
+# include/tlod_roi.h: the RoIPool backward with the reference gather's membership tests, a
+# fourth table with its own header (ledger: tests/test_abi.py, guard case in
+# tests/test_abi_guard_gpu.py)
+ROI_SIGNATURES = {
+    "tlod_roi_pool_bwd_gather_f32": (c_int, [P, P, c_int, c_int, c_int, c_int, P, c_int, c_int,
+                                             c_int, c_float, P, P]),
+}
+
 _lib = None
 
 
@@ -269,7 +277,8 @@ def lib():
                 "`python -c 'import __graft_entry__ as g; g.build()'` (no CPU fallback exists)")
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items())
-                                  + list(PA_ATF_SIGNATURES.items())):
+                                  + list(PA_ATF_SIGNATURES.items())
+                                  + list(ROI_SIGNATURES.items())):
             if os.environ.get("TLOD_LIB") and not hasattr(L, name):
                 continue  # an older tuning build (A/B timing) may predate an entry point
             fn = getattr(L, name)

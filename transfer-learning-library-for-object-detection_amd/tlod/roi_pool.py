@@ -2,7 +2,9 @@
 
 ``_RoIPooling(pooled_height, pooled_width, spatial_scale)`` as in modules/roi_pool.py:5-14.
 Forward keeps the int32 argmax (flat input index, -1 if empty) like the reference; the
-backward scatters through it in libtlod instead of the reference's per-input gather.
+backward scatters through it in libtlod instead of the reference's per-input gather, with
+the gather's membership tests (``tlod_roi_pool_bwd_gather_f32``, include/tlod_roi.h: a RoI
+whose rounded extent is inverted passes no gradient).
 """
 import torch
 from torch.nn import Module
@@ -24,21 +26,21 @@ class RoIPoolFunction(torch.autograd.Function):
         _lib.check(_lib.lib().tlod_roi_pool_fwd_f32(
             _lib.ptr(feat), B, C, H, W, _lib.ptr(rois_c), R, ph, pw, float(spatial_scale),
             _lib.ptr(out), _lib.ptr(argmax), _lib.stream_of(feat)), "roi_pool_fwd")
-        ctx.save_for_backward(argmax)
-        ctx.meta = (B, C, H, W)
+        ctx.save_for_backward(argmax, rois_c)
+        ctx.meta = (B, C, H, W, float(spatial_scale))
         ctx.mark_non_differentiable(argmax)
         return out, argmax
 
     @staticmethod
     def backward(ctx, grad_output, _grad_argmax=None):
-        (argmax,) = ctx.saved_tensors
-        B, C, H, W = ctx.meta
+        argmax, rois_c = ctx.saved_tensors
+        B, C, H, W, sc = ctx.meta
         g = grad_output.contiguous()
         R, _, ph, pw = g.shape
         grad_in = torch.zeros((B, C, H, W), dtype=g.dtype, device=g.device)
-        _lib.check(_lib.lib().tlod_roi_pool_bwd_f32(
-            _lib.ptr(g), _lib.ptr(argmax), R, C, ph, pw, _lib.ptr(grad_in), _lib.stream_of(g)),
-            "roi_pool_bwd")
+        _lib.check(_lib.lib().tlod_roi_pool_bwd_gather_f32(
+            _lib.ptr(g), _lib.ptr(argmax), B, C, H, W, _lib.ptr(rois_c), R, ph, pw, sc,
+            _lib.ptr(grad_in), _lib.stream_of(g)), "roi_pool_bwd")
         return grad_in, None, None, None, None
 
 
