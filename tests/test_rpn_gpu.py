@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+from device_rng import _rng_key  # noqa: F401  (tests/test_abi_guard_gpu.py reads it from here)
 from helpers import gt_set, rpn_outputs
 from oracle import rpn as orpn
 from oracle.boxes import generate_anchors
@@ -106,19 +107,6 @@ def test_anchor_target_device_rng_distribution():
         assert (l == 1).sum() <= 128
     assert not all(np.array_equal(labs[0], l) for l in labs[1:])
     del full
-
-
-def _rng_key(seed, stream, idx):
-    """(rng_u64(seed, stream, idx) >> 32) of csrc/common.h (splitmix64 twice), in numpy."""
-    def mix(z):
-        z = z + np.uint64(0x9e3779b97f4a7c15)
-        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xbf58476d1ce4e5b9)
-        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94d049bb133111eb)
-        return z ^ (z >> np.uint64(31))
-    with np.errstate(over="ignore"):
-        base = mix(np.array([seed], np.uint64) ^ (np.array([stream], np.uint64) *
-                                                  np.uint64(0xd1b54a32d192ed03)))
-        return (mix(base + idx.astype(np.uint64)) >> np.uint64(32)).astype(np.uint32)
 
 
 @pytest.mark.parametrize("H,W,seed", [(37, 75, 5), (38, 75, 77), (20, 30, 3), (50, 100, 9)])
