@@ -14,55 +14,14 @@ import math
 import pytest
 import torch
 
-pytestmark = pytest.mark.gpu
+from fused_optim import B1, B2, EPS, Truth, check_bar  # shared with test_fused_optim_*.py
 
-B1, B2, EPS = 0.9, 0.999, 1e-8
+pytestmark = pytest.mark.gpu
 
 
 def two_groups(ws, bs, lr=0.01):
     return [{"params": ws, "lr": lr, "weight_decay": 5e-4},
             {"params": bs, "lr": 2 * lr, "weight_decay": 0.0}]
-
-
-class Truth:
-    """clip_gradient + the optimizer's update in fp64 (the clip scale in fp64 too).  Adam:
-    d = g + wd*p; m = b1*m + (1-b1)*d; v = b2*v + (1-b2)*d*d;
-    p -= (lr / (1-b1^t)) * m / (sqrt(v) / sqrt(1-b2^t) + eps), t the parameter's own count.
-    SGD: d = g + wd*p; buf = mom*buf + d; p -= lr*buf."""
-
-    def __init__(self, groups, clip, kind="adam", momentum=0.9):
-        self.kind, self.clip, self.momentum = kind, clip, momentum
-        self.groups = [dict(g, params=[p.detach().double().clone() for p in g["params"]])
-                       for g in groups]
-        self.params = [p for g in self.groups for p in g["params"]]
-        self.m = [torch.zeros_like(p) for p in self.params]
-        self.v = [torch.zeros_like(p) for p in self.params]
-        self.t = [0] * len(self.params)
-
-    def step(self, grads):
-        gs = [None if g is None else g.detach().double() for g in grads]
-        s = 1.0
-        if self.clip > 0:
-            tot = math.sqrt(sum(float((g * g).sum()) for g in gs if g is not None))
-            s = self.clip / max(tot, self.clip)
-        i = -1
-        for grp in self.groups:
-            lr, wd = grp["lr"], grp["weight_decay"]
-            for p in grp["params"]:
-                i += 1
-                if gs[i] is None:
-                    continue
-                d = gs[i] * s + wd * p
-                if self.kind == "sgd":
-                    self.m[i] = self.momentum * self.m[i] + d
-                    p -= lr * self.m[i]
-                    continue
-                self.t[i] += 1
-                t = self.t[i]
-                self.m[i] = B1 * self.m[i] + (1 - B1) * d
-                self.v[i] = B2 * self.v[i] + (1 - B2) * d * d
-                p -= (lr / (1 - B1 ** t)) * self.m[i] / (
-                    self.v[i].sqrt() / math.sqrt(1 - B2 ** t) + EPS)
 
 
 def torch_step(opt, params, grads, clip):
@@ -84,24 +43,6 @@ def fused_step(opt, params, grads):
         if g is not None:
             p.grad = g.clone()
     return opt.step()
-
-
-def check_bar(fused, ref, truth, what=""):
-    """max |fused - truth| <= max(2 * max |ref - truth|, 4 ulp of max |truth|), per tensor;
-    returns the largest fused / torch error ratio seen (printed for DESIGN.md)."""
-    worst = 0.0
-    for i, (f, r, t) in enumerate(zip(fused, ref, truth)):
-        e_f = float((f.detach().double() - t).abs().max())
-        e_t = float((r.detach().double() - t).abs().max())
-        top = float(t.abs().max())
-        ulp = 2.0 ** (math.floor(math.log2(top)) - 23) if top > 0 else 2.0 ** -149
-        bar = max(2 * e_t, 4 * ulp)
-        print(f"{what} tensor {i}: E_fused {e_f:.3e}  E_torch {e_t:.3e}  "
-              f"ratio {e_f / e_t if e_t else float('nan'):.3f}  4ulp {4 * ulp:.3e}")
-        assert e_f <= bar, (what, i, e_f, e_t, 4 * ulp)
-        if e_t:
-            worst = max(worst, e_f / e_t)
-    return worst
 
 
 def clones(params):

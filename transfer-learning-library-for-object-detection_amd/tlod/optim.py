@@ -6,7 +6,8 @@ by ``torch.optim.SGD(params, momentum=0.9)`` with the reference's param groups
 (methods/DAF/DAF_train.py:311-325: biases lr*(DOUBLE_BIAS+1) and no weight decay unless
 BIAS_DECAY; weights lr and WEIGHT_DECAY) — three launches, no host wait: the gradients
 live in the persistent arena (tlod.grads), so the descriptor table is built and uploaded
-once per (arena layout, set of parameters with a gradient, learning rates).
+once per (arena layout, set of parameters with a gradient, learning rates and weight
+decays).
 
 3x3 conv weights are updated by tiles that also write their split-bf16 packs (the conv
 kernels' operand layouts, tlod_sgd_clip_pack_f32): the optimizer marks them as owned
@@ -166,7 +167,9 @@ class FusedClipOptimizer:
         (negative counts) only enter the gradient norm."""
         a = self.arena
         act = a.active if a is not None and a.active is not None else None
+        # (the rows bake in lr and weight decay: either changed in a group means a new table)
         tail = tuple(g["lr"] for g in self.param_groups) + \
+            tuple(g.get("weight_decay", 0.0) for g in self.param_groups) + \
             (0 if act is None else act.data_ptr(), _conv.PACK_GEN[0] if self.fused_packs else 0)
         # fast key: with the arena, a step in which every parameter's gradient arrived has
         # every gradient in its fixed slot (GradArena._on_grad), so the table depends only on
@@ -301,7 +304,7 @@ class FusedClipOptimizer:
                 if k in s:
                     g[k] = s[k]
         self._stepped = set(state)
-        self._tables.clear()  # (weight_decay is not part of the table key)
+        self._tables.clear()
         self._last_hit = None
 
 
