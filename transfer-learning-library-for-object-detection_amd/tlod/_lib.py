@@ -264,6 +264,16 @@ ROI_SIGNATURES = {
                                              c_int, c_float, P, P]),
 }
 
+# include/tlod_selftrain.h: the IDF self-training extension (pseudo ground truth packed from the
+# detections, the domain losses with EFocalLoss), a fifth table with its own header (ledger and
+# guard cases: tests/test_selftrain_cpu.py, tests/test_selftrain_gpu.py)
+SELFTRAIN_SIGNATURES = {
+    "tlod_pseudo_gt_f32": (c_int, [P, P, c_int, c_int, c_double, c_int, c_uint64, P, P, P]),
+    "tlod_idf_domain_loss_ef_f32": (c_int, [P, c_int, c_int, P, c_int, c_int, c_float, P, P]),
+    "tlod_idf_domain_loss_ef_bwd_f32": (c_int, [P, c_int, c_int, P, c_int, c_int, c_float, P, P,
+                                                P, P]),
+}
+
 _lib = None
 
 
@@ -278,7 +288,8 @@ def lib():
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items())
                                   + list(PA_ATF_SIGNATURES.items())
-                                  + list(ROI_SIGNATURES.items())):
+                                  + list(ROI_SIGNATURES.items())
+                                  + list(SELFTRAIN_SIGNATURES.items())):
             if os.environ.get("TLOD_LIB") and not hasattr(L, name):
                 continue  # an older tuning build (A/B timing) may predate an entry point
             fn = getattr(L, name)

@@ -20,7 +20,8 @@ the main stack's RPN proposals, proposal target and fc6 / fc7 for the instance d
 
 Device ops (csrc/idf.hip, include/tlod_idf.h): one DAM launch pair per map, and one autograd
 function (``_Separation``) for distance + both modulations, forward and backward one entry
-each; the seven domain losses of an image are one launch each way (``_DomainLoss``).
+each; the seven domain losses of an image are one launch each way (``_DomainLoss``; with
+``ef=True`` the instance term is EFocalLoss, csrc/selftrain.hip).
 ``TLOD_FUSED_IDF=0`` takes the torch compositions of the same math instead.
 
 The distance reduces over the channel axis with eps added to the difference — PyTorch 0.4's
@@ -88,10 +89,18 @@ def focal_loss_torch(z, label, gamma):
     return (-(1 - p).pow(gamma) * p.log()).mean()
 
 
-def domain_losses_torch(z_img, label_img, z_ins, label_ins, gamma):
+def efocal_loss_torch(z, label, gamma):
+    """EFocalLoss(class_num=2, gamma) (net_utils.py:73-102, IDF_train.py --ef) for one label:
+    mean -exp(-gamma p) log p, alpha 1 and, unlike FocalLoss, no clamp."""
+    p = F.softmax(z, dim=1)[:, int(label)]
+    return (-torch.exp(-gamma * p) * p.log()).mean()
+
+
+def domain_losses_torch(z_img, label_img, z_ins, label_ins, gamma, ef=False):
     y = torch.full((z_img.shape[0],), int(label_img), dtype=torch.long, device=z_img.device)
     ce = F.cross_entropy(z_img, y, reduction="none")
-    return torch.cat([ce, focal_loss_torch(z_ins, label_ins, gamma).view(1)])
+    ins = (efocal_loss_torch if ef else focal_loss_torch)(z_ins, label_ins, gamma)
+    return torch.cat([ce, ins.view(1)])
 
 
 # ------------------------------------------------------------------------------ device ops
@@ -181,39 +190,43 @@ def plain_distance(a, b):
 
 
 class _DomainLoss(torch.autograd.Function):
-    """z_img (n, 2), z_ins (R, 2) -> (n + 1) losses: tlod_idf_domain_loss_f32 / _bwd_f32."""
+    """z_img (n, 2), z_ins (R, 2) -> (n + 1) losses: tlod_idf_domain_loss_f32 / _bwd_f32, or
+    with ``ef`` tlod_idf_domain_loss_ef_f32 / _ef_bwd_f32 (include/tlod_selftrain.h)."""
 
     @staticmethod
-    def forward(ctx, z_img, z_ins, label_img, label_ins, gamma):
+    def forward(ctx, z_img, z_ins, label_img, label_ins, gamma, ef=False):
         _lib.require_cuda(z_img, z_ins)
         zi, zn = z_img.detach().contiguous().float(), z_ins.detach().contiguous().float()
         assert zi.dim() == 2 and zi.shape[1] == 2 and zn.dim() == 2 and zn.shape[1] == 2
         loss = torch.empty(zi.shape[0] + 1, dtype=torch.float32, device=zi.device)
-        _lib.check(_lib.lib().tlod_idf_domain_loss_f32(
+        L = _lib.lib()
+        _lib.check((L.tlod_idf_domain_loss_ef_f32 if ef else L.tlod_idf_domain_loss_f32)(
             _lib.ptr(zi), zi.shape[0], int(label_img), _lib.ptr(zn), zn.shape[0], int(label_ins),
             float(gamma), _lib.ptr(loss), _lib.stream_of(zi)), "idf_domain_loss")
-        ctx.args = (int(label_img), int(label_ins), float(gamma))
+        ctx.args = (int(label_img), int(label_ins), float(gamma), bool(ef))
         ctx.save_for_backward(zi, zn)
         return loss
 
     @staticmethod
     def backward(ctx, g):
         zi, zn = ctx.saved_tensors
-        label_img, label_ins, gamma = ctx.args
+        label_img, label_ins, gamma, ef = ctx.args
         g = g.contiguous().float()
         dzi, dzn = torch.empty_like(zi), torch.empty_like(zn)
-        _lib.check(_lib.lib().tlod_idf_domain_loss_bwd_f32(
+        L = _lib.lib()
+        _lib.check((L.tlod_idf_domain_loss_ef_bwd_f32 if ef else L.tlod_idf_domain_loss_bwd_f32)(
             _lib.ptr(zi), zi.shape[0], label_img, _lib.ptr(zn), zn.shape[0], label_ins, gamma,
             _lib.ptr(g), _lib.ptr(dzi), _lib.ptr(dzn), _lib.stream_of(zi)), "idf_domain_loss_bwd")
-        return dzi, dzn, None, None, None
+        return dzi, dzn, None, None, None, None
 
 
-def domain_losses(z_img, label_img, z_ins, label_ins, gamma=3.0):
+def domain_losses(z_img, label_img, z_ins, label_ins, gamma=3.0, ef=False):
     """The n two-logit cross entropies of z_img (n, 2) against label_img and the focal loss of
-    z_ins (R, 2) against label_ins as one (n + 1) vector; weights not folded in."""
+    z_ins (R, 2) against label_ins (``ef``: EFocalLoss, IDF_train.py:162-165) as one (n + 1)
+    vector; weights not folded in."""
     if not fused_idf():
-        return domain_losses_torch(z_img, label_img, z_ins, label_ins, gamma)
-    return _DomainLoss.apply(z_img, z_ins, label_img, label_ins, gamma)
+        return domain_losses_torch(z_img, label_img, z_ins, label_ins, gamma, ef)
+    return _DomainLoss.apply(z_img, z_ins, label_img, label_ins, gamma, ef)
 
 
 # ------------------------------------------------------------------------------ modules
@@ -440,24 +453,31 @@ class _fasterRCNN(nn.Module):
                 dom[5], SE_WEIGHT * dist2, SE_WEIGHT * dist3, dist1.mean(), dist2, dist3)
 
     @staticmethod
-    def domain_terms(out, label, gamma=3.0):
+    def domain_terms(out, label, gamma=3.0, ef=False):
         """The seven unweighted domain losses of one call's outputs: CE of domain_1, domain_2,
         domain_3, domain_1_b, domain_2_b, domain_3_b against ``label`` and the focal loss of
-        domain_ins (IDF_train.py:242-270, 302-327)."""
-        return domain_losses(torch.cat(out[8:11] + out[12:15], 0), label, out[11], label, gamma)
+        domain_ins (IDF_train.py:242-270, 302-327; ``ef``: EFocalLoss, :162-165)."""
+        return domain_losses(torch.cat(out[8:11] + out[12:15], 0), label, out[11], label, gamma,
+                             ef)
 
     @classmethod
-    def total_loss(cls, out_s, out_t, separation=True, gamma=3.0):
+    def total_loss(cls, out_s, out_t, separation=True, gamma=3.0, ef=False, target_gate=None):
         """IDF_train.py:229-335: the source detection losses, 0.5 x the target call's, 0.5 x
         every image-level cross entropy (label 0 source, 1 target), 0.25 x the two focal
-        losses and, when ``separation``, the four loss_se terms."""
+        losses (``ef``: EFocalLoss) and, when ``separation``, the four loss_se terms.
+        target_gate: a device scalar (0 or 1) multiplied into the target call's four detection
+        losses (tlod.detector.train.idf_selftrain_step: an image without a pseudo label)."""
         scalars = list(out_s[3:7]) + list(out_t[3:7])
+        if target_gate is not None:
+            gate = target_gate.reshape(()).to(out_t[3].dtype)
+            scalars[4:] = [x.reshape(()) * gate for x in scalars[4:]]
         weights = [1.0] * 4 + [0.5] * 4
         if separation:
             scalars += [out_s[15], out_s[16], out_t[15], out_t[16]]
             weights += [1.0] * 4
         t = torch.cat([torch.stack([x.reshape(()) for x in scalars]),
-                       cls.domain_terms(out_s, 0, gamma), cls.domain_terms(out_t, 1, gamma)])
+                       cls.domain_terms(out_s, 0, gamma, ef),
+                       cls.domain_terms(out_t, 1, gamma, ef)])
         return _dot(t, weights + ([0.5] * 6 + [0.25]) * 2)
 
     def _init_weights(self):

@@ -193,10 +193,62 @@ def cityscape(image_set, year, devkit_path):
     return pascal_voc(image_set, year, devkit_path, CITYSCAPE_CLASSES, prefix="cityscape")
 
 
-def get_imdb(name, devkit_path, classes=None):
+class pseudo_voc(pascal_voc):
+    """A pseudo-labelled target set (step 3 of methods/IDF/IDF_train.sh): the VOC layout read as
+    the IDF loaders read it (lib/IDF/foggy_cityscape.py:239-242, lib/IDF/cityscape.py): every
+    coordinate is ``max(x - 1, 0)``.  A detection clipped to the image edge is written as 0;
+    ``pascal_voc``'s plain ``x - 1`` would hand the uint16 roidb a -1 (65535, or an OverflowError
+    from numpy 2 on).
+
+    ``devkit_path`` holds the annotations and the image-set file (tlod.eval.pseudo.save_labels);
+    the images are looked up there too, or under ``image_devkit`` when the labels were written
+    beside the target set, not into it."""
+
+    def __init__(self, image_set, year, devkit_path, classes=CITYSCAPE_CLASSES,
+                 image_devkit=None):
+        pascal_voc.__init__(self, image_set, year, devkit_path, classes, prefix="pseudo")
+        self._image_path = os.path.join(devkit_path if image_devkit is None else image_devkit,
+                                        "VOC" + year)
+
+    def image_path_from_index(self, index):
+        p = os.path.join(self._image_path, "JPEGImages", index + self._image_ext)
+        if not os.path.exists(p):
+            raise FileNotFoundError(f"Path does not exist: {p}")
+        return p
+
+    def _load_pascal_annotation(self, index):
+        tree = ET.parse(os.path.join(self._data_path, "Annotations", index + ".xml"))
+        objs = tree.findall("object")
+        n = len(objs)
+        boxes = np.zeros((n, 4), dtype=np.uint16)
+        gt_classes = np.zeros((n,), dtype=np.int32)
+        overlaps = np.zeros((n, self.num_classes), dtype=np.float32)
+        seg_areas = np.zeros((n,), dtype=np.float32)
+        ishards = np.zeros((n,), dtype=np.int32)
+        for ix, obj in enumerate(objs):
+            bbox = obj.find("bndbox")
+            x1, y1, x2, y2 = (max(float(bbox.find(k).text) - 1, 0)
+                              for k in ("xmin", "ymin", "xmax", "ymax"))
+            diffc = obj.find("difficult")
+            ishards[ix] = 0 if diffc is None else int(diffc.text)
+            cls = self._class_to_ind[obj.find("name").text.lower().strip()]
+            boxes[ix, :] = [x1, y1, x2, y2]
+            gt_classes[ix] = cls
+            overlaps[ix, cls] = 1.0
+            seg_areas[ix] = (x2 - x1 + 1) * (y2 - y1 + 1)
+        return {"boxes": boxes, "gt_classes": gt_classes, "gt_ishard": ishards,
+                "gt_overlaps": overlaps, "flipped": False, "seg_areas": seg_areas}
+
+
+def get_imdb(name, devkit_path, classes=None, image_devkit=None):
     """lib/datasets/factory.py:24-73 for the VOC-layout names: voc_<year>_<set>,
-    cityscape_<year>_<set>; a '+' joins several (combined_roidb)."""
+    cityscape_<year>_<set>, and pseudo_<year>_<set> for a pseudo-labelled set (``image_devkit``:
+    where its images live, when not under ``devkit_path``); a '+' joins several
+    (combined_roidb)."""
     parts = name.split("_")
+    if name.startswith("pseudo_") and len(parts) >= 3:
+        return pseudo_voc("_".join(parts[2:]), parts[1], devkit_path,
+                          CITYSCAPE_CLASSES if classes is None else classes, image_devkit)
     if name.startswith("voc_") and len(parts) >= 3:
         return pascal_voc("_".join(parts[2:]), parts[1], devkit_path,
                           VOC_CLASSES if classes is None else classes)

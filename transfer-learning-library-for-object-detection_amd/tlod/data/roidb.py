@@ -46,11 +46,15 @@ def filter_roidb(roidb):
     return [r for r in roidb if len(r["boxes"]) != 0]
 
 
-def combined_roidb(imdb_names, devkit_path, training=True, classes=None):
+def combined_roidb(imdb_names, devkit_path, training=True, classes=None, image_devkit=None):
     """roidb.py:89-130 -> (imdb, roidb, ratio_list, ratio_index).  Flipped copies are
-    appended when cfg.TRAIN.USE_FLIPPED (the training drivers set it True)."""
+    appended when cfg.TRAIN.USE_FLIPPED (the training drivers set it True).  image_devkit: where
+    a pseudo_<year>_<set>'s images live (tlod.data.imdb.pseudo_voc)."""
     def get_roidb(name):
-        imdb = get_imdb(name, devkit_path, classes)
+        if image_devkit is None:
+            imdb = get_imdb(name, devkit_path, classes)
+        else:
+            imdb = get_imdb(name, devkit_path, classes, image_devkit)
         if cfg.TRAIN.USE_FLIPPED:
             imdb.append_flipped_images()
         prepare_roidb(imdb)

@@ -237,12 +237,8 @@ def idf_forward(model, batch, separation=True, eta=1.0):
     return out_s, out_t
 
 
-def idf_train_step(model, optimizer, batch, separation=True, gamma=3.0, eta=1.0, reducer=None):
-    """One IDF iteration (methods/IDF/IDF_train.py:223-339) over the project's 10-tuple batch:
-    the source call on the ground truth, the target call (``target=True``) with the batch's
-    target gt_boxes / num_boxes as the pseudo boxes and the reference's single all-zero box
-    for the main stack (:277-280), the loss sum (model.total_loss), backward, update.  No
-    gradient clipping.  Returns the loss as a device tensor (no host sync)."""
+def _idf_step(model, optimizer, batch, separation, gamma, eta, reducer, ef, target_gate=None):
+    """zero_grad, the two calls, the loss sum, backward, update (no gradient clipping)."""
     from ..optim import FusedClipOptimizer
     fused = isinstance(optimizer, FusedClipOptimizer)
     if reducer is not None:
@@ -250,7 +246,10 @@ def idf_train_step(model, optimizer, batch, separation=True, gamma=3.0, eta=1.0,
     else:
         optimizer.zero_grad(set_to_none=True)
     out_s, out_t = idf_forward(model, batch, separation, eta)
-    loss = model.total_loss(out_s, out_t, separation, gamma)
+    if ef or target_gate is not None:
+        loss = model.total_loss(out_s, out_t, separation, gamma, ef, target_gate)
+    else:
+        loss = model.total_loss(out_s, out_t, separation, gamma)
     loss.backward()
     scale = 1.0
     if reducer is not None:
@@ -264,6 +263,53 @@ def idf_train_step(model, optimizer, batch, separation=True, gamma=3.0, eta=1.0,
             clip_gradient_([p for p in model.parameters()], clip)
         optimizer.step()
     return loss.detach()
+
+
+def idf_train_step(model, optimizer, batch, separation=True, gamma=3.0, eta=1.0, reducer=None,
+                   ef=False):
+    """One IDF iteration (methods/IDF/IDF_train.py:223-339) over the project's 10-tuple batch:
+    the source call on the ground truth, the target call (``target=True``) with the batch's
+    target gt_boxes / num_boxes as the pseudo boxes and the reference's single all-zero box
+    for the main stack (:277-280), the loss sum (model.total_loss; ``ef``: EFocalLoss on the
+    instance rows, :162-165), backward, update.  No gradient clipping.  Returns the loss as a
+    device tensor (no host sync)."""
+    return _idf_step(model, optimizer, batch, separation, gamma, eta, reducer, ef)
+
+
+SELFTRAIN_SEED_OFFSET = 104729  # keeps the labels' draws apart from the sampling layers' seeds
+
+
+def idf_selftrain_step(model, labeler, optimizer, batch, thresh=0.5, seed=None, ef=False,
+                       separation=True, gamma=3.0, eta=1.0, reducer=None, class_agnostic=False,
+                       max_gt=None, im_info_host=None):
+    """One IDF iteration whose pseudo boxes are made inside the step (online self-training):
+    ``labeler`` — a frozen eval-mode detector, e.g. ``build_model("faster_rcnn", ...).eval()`` —
+    labels the batch's target image (tlod.eval.pseudo.label_image: its forward, tlod_detect_f32
+    at ``thresh``, tlod_pseudo_gt_f32), and idf_train_step's body runs with those boxes in place
+    of ``batch[7:9]``.
+
+    A target image that gets no label contributes its domain and separation terms only: the
+    target call's four detection losses are multiplied by ``num_boxes_p > 0`` on the device.
+    (The reference labels offline and its roidb filter drops such an image from the target set
+    altogether; inside a step there is nothing to skip to without a host sync.)
+
+    seed: the base of the labels' random cap (None: cfg.RNG_SEED); the per-step seed is derived
+    from it and a call counter kept on ``model``, as the sampling layers derive theirs.
+    im_info_host: (height, width, scale) of the target blob as host numbers; without it
+    ``batch[6]`` is read back, which is the step's one host sync.
+    Returns (loss, num_boxes_p), device tensors."""
+    from ..eval.pseudo import label_image
+    if im_info_host is None:
+        im_info_host = batch[6].reshape(-1, 3)[0].tolist()
+    calls = getattr(model, "_selftrain_calls", 0) + 1
+    model._selftrain_calls = calls
+    base = int(cfg.RNG_SEED if seed is None else seed) + SELFTRAIN_SEED_OFFSET
+    gt_p, num_p = label_image(labeler, batch[5], im_info_host, thresh, class_agnostic, max_gt,
+                              seed=(base * 1000003 + calls) & 0xFFFFFFFFFFFFFFFF)
+    batch = tuple(batch[:7]) + (gt_p, num_p) + tuple(batch[9:])
+    loss = _idf_step(model, optimizer, batch, separation, gamma, eta, reducer, ef,
+                     target_gate=num_p > 0)
+    return loss, num_p
 
 
 def smoke_step(device, method="daf", net="vgg16"):
