@@ -139,6 +139,11 @@ __device__ float raw_buffer_load_f32(i32x4 rsrc, int voffset, int soffset, int a
 // (a store at an offset past the range — kBufOOB — is dropped by the hardware)
 __device__ void raw_buffer_store_f32(float v, i32x4 rsrc, int voffset, int soffset, int aux)
     __asm("llvm.amdgcn.raw.buffer.store.f32");
+// 8- and 16-B stores: dword alignment suffices (as for the 16-B loads)
+__device__ void raw_buffer_store_v2f32(f32x2_t v, i32x4 rsrc, int voffset, int soffset, int aux)
+    __asm("llvm.amdgcn.raw.buffer.store.v2f32");
+__device__ void raw_buffer_store_v4f32(f32x4v v, i32x4 rsrc, int voffset, int soffset, int aux)
+    __asm("llvm.amdgcn.raw.buffer.store.v4f32");
 
 __device__ __forceinline__ i32x4 make_buffer_rsrc(const void* p, unsigned bytes) {
   struct __attribute__((packed)) R {

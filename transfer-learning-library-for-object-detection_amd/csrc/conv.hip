@@ -20,6 +20,7 @@
 #include "common.h"
 #include "bs_common.h"
 #include "tlod.h"
+#include "tlod_plan.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -828,6 +829,63 @@ __device__ __forceinline__ void bs_mac16(f32x4& acc, const V (&a)[3], const V (&
   }
 }
 
+// The warp-specialized kernel passes the pixel fragment as the MFMA's A operand and the
+// weight fragment as B (the two fragment layouts are the same: lane % 16 = row, lane / 16 =
+// k-octet), so a lane's four accumulator registers are four consecutive pixels of one
+// channel and go out in one 16-B store.  bs_mac16 keeps its (weight plane, pixel plane)
+// order of products; only the operand slots swap.
+__device__ __forceinline__ f32x4 mfma16_bf16_pa(u32x4 w, u32x4 x, f32x4 c) {
+  return mfma16_bf16(x, w, c);
+}
+__device__ __forceinline__ f32x4 mfma16k16_bf16_pa(u32x2 w, u32x2 x, f32x4 c) {
+  return mfma16k16_bf16(x, w, c);
+}
+
+// Direct epilogue of conv_fwd_bs_ws_kernel: how the four pixels q0 .. q0 + 3 (row-major in
+// the TH x TW tile at (h0, w0) of an H x W map; q0 % 4 == 0) of one lane are stored.
+//   kWsRun      one 16-B store: all four inside the tile, in one tile row and inside the map
+//   kWsPartial  per element (the group straddles a tile-row end, the tile's end or the
+//               map's right edge; elements outside the tile or the map are dropped)
+//   kWsNone     nothing of the group is inside the tile and the map
+// The buffer range check cannot stand in for any of this: a pixel past a row's end lands in
+// the next row, inside the range.  (r, c) is q0's position in the tile.  ws_tile's tiles are
+// at least 8 wide, so a group wraps at most once.
+enum { kWsNone = 0, kWsRun = 1, kWsPartial = 2 };
+struct WsGroup {
+  int kind, r, c;
+};
+// element e of the group at (r, c): its tile position, and whether it is stored
+__host__ __device__ inline bool ws_group_elem(int r, int c, int e, int TH, int TW, int h0,
+                                              int w0, int H, int W, int* er, int* ec) {
+  const int wrap = c + e >= TW;
+  *er = r + wrap;
+  *ec = c + e - (wrap ? TW : 0);
+  return *er < TH && h0 + *er < H && w0 + *ec < W;
+}
+__host__ __device__ inline WsGroup ws_group(int q0, int TH, int TW, int h0, int w0, int H,
+                                            int W) {
+  WsGroup gk{kWsNone, q0 / TW, q0 % TW};
+  if (gk.r >= TH) return gk;
+  if (gk.c + 3 < TW && h0 + gk.r < H && w0 + gk.c + 3 < W) {
+    gk.kind = kWsRun;
+    return gk;
+  }
+  for (int e = 0; e < 4; ++e) {
+    int er, ec;
+    if (ws_group_elem(gk.r, gk.c, e, TH, TW, h0, w0, H, W, &er, &ec)) gk.kind = kWsPartial;
+  }
+  return gk;
+}
+
+// Pooling epilogue of conv_fwd_bs_ws_kernel: how a lane's two pooled outputs (hp, wp) and
+// (hp, wp + 1), wp even, of an Hp x Wp pooled map are stored: one 8-B store, the first alone
+// (an odd Wp's last column), or nothing (the tile's pixels past the map).
+enum { kWsPoolNone = 0, kWsPoolOne = 1, kWsPoolPair = 2 };
+__host__ __device__ inline int ws_pool_store(int hp, int wp, int Hp, int Wp) {
+  if (hp >= Hp || wp >= Wp) return kWsPoolNone;
+  return wp + 1 < Wp ? kWsPoolPair : kWsPoolOne;
+}
+
 // The work item of workgroup v: a whole tile (direct) or one split-K piece of a tail tile,
 // decoded exactly as conv_fwd_bs_kernel decodes its block id.
 struct WsItem {
@@ -993,7 +1051,8 @@ __global__ void __launch_bounds__(WM* WN * 64 + kProdWaves * 64)
 
   // ================= MFMA waves
   // The wave's 64 x 64 output block is 4 x 4 tiles of 16 x 16 (row block rb = 16 output
-  // channels; column block cb = 16 pixels).  One k-step takes four (tap, 8-channel) units,
+  // channels; column block cb = 16 pixels; the pixels are the MFMA's A operand, see
+  // mfma16_bf16_pa).  One k-step takes four (tap, 8-channel) units,
   // lane group g = lane / 16 reading unit 4s + g; the 16x16x16 step takes units 16, 17
   // (lanes 0-31 / 32-63, 8-B halves by (lane / 16) & 1).
   const int lane = tid & 63, wid = tid >> 6;
@@ -1061,7 +1120,7 @@ __global__ void __launch_bounds__(WM* WN * 64 + kProdWaves * 64)
         b[pl] = u32x4{lo[0], lo[1], hi[0], hi[1]};
       }
 #pragma unroll
-      for (int rb = 0; rb < RB; ++rb) bs_mac16<NP>(acc[rb][cb], a[rb], b, mfma16_bf16);
+      for (int rb = 0; rb < RB; ++rb) bs_mac16<NP>(acc[rb][cb], a[rb], b, mfma16_bf16_pa);
     }
   };
   auto step8 = [&](int ao, int bo) {
@@ -1078,7 +1137,7 @@ __global__ void __launch_bounds__(WM* WN * 64 + kProdWaves * 64)
       for (int pl = 0; pl < C::NPL; ++pl)
         b[pl] = *reinterpret_cast<const u32x2*>(smem + baddr(cb, bo) + pl * C::B_PLANE);
 #pragma unroll
-      for (int rb = 0; rb < RB; ++rb) bs_mac16<NP>(acc[rb][cb], a[rb], b, mfma16k16_bf16);
+      for (int rb = 0; rb < RB; ++rb) bs_mac16<NP>(acc[rb][cb], a[rb], b, mfma16k16_bf16_pa);
     }
   };
 
@@ -1136,61 +1195,77 @@ __global__ void __launch_bounds__(WM* WN * 64 + kProdWaves * 64)
     __syncthreads();
   }
 
-  // epilogue: the lane holds rows 4g..4g+3 of column l16 of each 16 x 16 tile
-  if (!it.direct) {
-    float* St = slab + ((size_t)it.split * n_tail + it.ti) * C::BM * TP;
+  // epilogue: pixels are the MFMA's rows (mfma16_bf16_pa), so in acc[rb][cb] the lane holds
+  // pixels q0 .. q0 + 3, q0 = 64 wn + 16 cb + 4 g, of channel 16 rb + l16 of the wave's block
+  const int mlane = wm * MI * 32 + l16;
+  if (!it.direct) {  // one 16-B store per tile (slab rows are TP = 512 floats)
+    float* St = slab + (((size_t)it.split * n_tail + it.ti) * C::BM + mlane) * TP + wn * 64 + 4 * g;
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
       for (int cb = 0; cb < CB; ++cb)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int ml = wm * MI * 32 + rb * 16 + 4 * g + r;
-          St[ml * TP + wn * 64 + cb * 16 + l16] = acc[rb][cb][r];
-        }
+        *reinterpret_cast<f32x4*>(St + rb * 16 * TP + cb * 16) = acc[rb][cb];
     return;
   }
   if constexpr (NJ == 2) {
     if (epi.pool) {
       // max_pool2d(2, 2) window (16 x 32 tiles only, see ws_tile): pixel rows j = 0, 1
-      // (column blocks hh and 2 + hh), columns (l16, l16 ^ 1); torch's window order and
-      // update rule, as conv_fwd_bs_kernel
+      // (column blocks hh and 2 + hh), columns 16 hh + 4 g + (2 p, 2 p + 1) = registers (2 p,
+      // 2 p + 1) of the lane; torch's window order and update rule, as conv_fwd_bs_kernel.
+      // The lane's two pooled outputs are neighbours in a pooled row: one 8-B store.
       const int Hp = H / 2, Wp2 = W / 2;
-      float* Pn = epi.pool + (size_t)it.n * Cout * Hp * Wp2;
+      const i32x4 p_rsrc = make_buffer_rsrc(epi.pool + (size_t)it.n * Cout * Hp * Wp2,
+                                            (unsigned)Cout * Hp * Wp2 * 4u);
       const int hp = (it.h0 + wn * NJ) / 2;
 #pragma unroll
       for (int hh = 0; hh < 2; ++hh) {
-        const int wp = (it.w0 + hh * 16 + l16) / 2;
-        const bool writer = (l16 & 1) == 0 && hp < Hp && wp < Wp2;
+        const int wp = (it.w0 + hh * 16 + 4 * g) / 2;
+        const int pk = ws_pool_store(hp, wp, Hp, Wp2);
 #pragma unroll
-        for (int rb = 0; rb < RB; ++rb)
+        for (int rb = 0; rb < RB; ++rb) {
+          const int ml = mlane + rb * 16;
+          const float sc = scale_s[ml], bi = bias_s[ml];
+          float m2[2];
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int ml = wm * MI * 32 + rb * 16 + 4 * g + r;
-            float v2[2];
+          for (int p = 0; p < 2; ++p) {
+            float v[2][2];  // [pixel row][column]
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
-              v2[j] = acc[rb][j * 2 + hh][r];
-              if (has_scale) v2[j] *= scale_s[ml];
-              v2[j] += bias_s[ml];
-              if (epi.relu) v2[j] = fmaxf(v2[j], 0.f);
-            }
-            const float c0 = __shfl_xor(v2[0], 1), c1 = __shfl_xor(v2[1], 1);
-            float m = v2[0];
-            if (c0 > m || __builtin_isnan(c0)) m = c0;
-            if (v2[1] > m || __builtin_isnan(v2[1])) m = v2[1];
-            if (c1 > m || __builtin_isnan(c1)) m = c1;
-            if (writer && it.m0 + ml < Cout) Pn[((size_t)(it.m0 + ml) * Hp + hp) * Wp2 + wp] = m;
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+              for (int k = 0; k < 2; ++k) {
+                float t = acc[rb][j * 2 + hh][2 * p + k];
+                if (has_scale) t *= sc;
+                t += bi;
+                if (epi.relu) t = fmaxf(t, 0.f);
+                v[j][k] = t;
+              }
+            float m = v[0][0];
+            if (v[0][1] > m || __builtin_isnan(v[0][1])) m = v[0][1];
+            if (v[1][0] > m || __builtin_isnan(v[1][0])) m = v[1][0];
+            if (v[1][1] > m || __builtin_isnan(v[1][1])) m = v[1][1];
+            m2[p] = m;
           }
+          const int co = it.m0 + ml;
+          const int o = ((co * Hp + hp) * Wp2 + wp) * 4;
+          if (co < Cout) {
+            if (pk == kWsPoolPair)
+              raw_buffer_store_v2f32(f32x2_t{m2[0], m2[1]}, p_rsrc, o, 0, 0);
+            else if (pk == kWsPoolOne)
+              raw_buffer_store_f32(m2[0], p_rsrc, o, 0, 0);
+          }
+        }
       }
       return;
     }
   }
-  // Branch-free: 32-bit offsets into the image's planes through buffer resources; an
-  // element outside the tile / map / Cout gets offset kBufOOB, which the hardware drops
-  // (store) or reads as 0 (residual / mask load).  The per-element bounds checks and 64-bit
-  // addresses of a plain store epilogue compiled to ~10 branchy instructions per element:
-  // 29k of a tile's 317k cycles with the stores themselves removed (round 4).
+  // 32-bit offsets into the image's planes through buffer resources.  A run (ws_group) is
+  // one 16-B store, branch-free: a group that is no run, or a channel past Cout, takes offset
+  // kBufOOB, which the hardware drops (store) or reads as 0 (residual / mask load).  The
+  // groups that are partial are stored per element under the same rule; a column block none
+  // of whose four lane groups is partial (wave-uniform, decided here once) skips that.
+  // (The per-element bounds checks and 64-bit addresses of a plain store epilogue compiled
+  // to ~10 branchy instructions per element: 29k of a tile's 317k cycles with the stores
+  // themselves removed, round 4.)
   const size_t img_off = (size_t)it.n * Cout * HWi;
   const unsigned plane_bytes = (unsigned)Cout * HWi * 4u;
   const i32x4 y_rsrc = make_buffer_rsrc(Y + img_off, plane_bytes);
@@ -1198,45 +1273,70 @@ __global__ void __launch_bounds__(WM* WN * 64 + kProdWaves * 64)
   const float* Mn = epi.mask ? epi.mask + img_off : nullptr;
   const i32x4 r_rsrc = make_buffer_rsrc(Rn ? Rn : Y, Rn ? plane_bytes : 0u);
   const i32x4 m_rsrc = make_buffer_rsrc(Mn ? Mn : Y, Mn ? plane_bytes : 0u);
-  int pixo[CB];  // byte offset of the lane's pixel in a channel plane (-1: none)
+  int goff[CB];   // run: byte offset of its first pixel in a channel plane (else -1)
+  int prc[CB];    // partial group: its tile position r << 16 | c (else -1)
+  bool part[CB];  // some lane group of the column block is partial
 #pragma unroll
   for (int cb = 0; cb < CB; ++cb) {
-    const int q = wn * 64 + cb * 16 + l16;
-    const int h = it.h0 + q / TW, w = it.w0 + q % TW;
-    pixo[cb] = q < TH * TW && h < H && w < W ? (h * W + w) * 4 : -1;
+    const WsGroup gk = ws_group(wn * 64 + cb * 16 + 4 * g, TH, TW, it.h0, it.w0, H, W);
+    goff[cb] = gk.kind == kWsRun ? ((it.h0 + gk.r) * W + it.w0 + gk.c) * 4 : -1;
+    prc[cb] = gk.kind == kWsPartial ? (gk.r << 16 | gk.c) : -1;
+    part[cb] = __any(gk.kind == kWsPartial) != 0;
   }
+  auto finish = [&](float val, float sc, float bi, float ext, float msk) {
+    if (has_scale) val *= sc;
+    val += bi;
+    if (Rn) val += ext;
+    if (epi.relu) val = fmaxf(val, 0.f);
+    if (Mn && !(msk > 0.f)) val = 0.f;
+    return val;
+  };
 #pragma unroll
   for (int rb = 0; rb < RB; ++rb) {
-    int off[CB][4];
+    const int ml = mlane + rb * 16, co = it.m0 + ml;
+    const int rowo = co < Cout ? co * HWi * 4 : -1;
+    const float sc = scale_s[ml], bi = bias_s[ml];
+    int off[CB];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int co = it.m0 + wm * MI * 32 + rb * 16 + 4 * g + r;
-      const int rowo = co < Cout ? co * HWi * 4 : -1;
+    for (int cb = 0; cb < CB; ++cb) off[cb] = (rowo | goff[cb]) >= 0 ? rowo + goff[cb] : kBufOOB;
+    // residual / mask operands of the row block — the runs' 16-B ones and the partial groups'
+    // per-element ones — loaded together, ahead of its stores
+    f32x4 ext[CB], msk[CB];
 #pragma unroll
-      for (int cb = 0; cb < CB; ++cb) off[cb][r] = (rowo | pixo[cb]) >= 0 ? rowo + pixo[cb] : kBufOOB;
+    for (int cb = 0; cb < CB; ++cb) {
+      ext[cb] = Rn ? raw_buffer_load_v4f32(r_rsrc, off[cb], 0, 0) : f32x4{0.f, 0.f, 0.f, 0.f};
+      msk[cb] = Mn ? raw_buffer_load_v4f32(m_rsrc, off[cb], 0, 0) : f32x4{1.f, 1.f, 1.f, 1.f};
     }
-    // residual / mask operands of the row block loaded together, ahead of its stores
-    float ext[CB][4], msk[CB][4];
+    int eo[CB][4];
+    float e4[CB][4], m4[CB][4];
 #pragma unroll
-    for (int cb = 0; cb < CB; ++cb)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        ext[cb][r] = Rn ? raw_buffer_load_f32(r_rsrc, off[cb][r], 0, 0) : 0.f;
-        msk[cb][r] = Mn ? raw_buffer_load_f32(m_rsrc, off[cb][r], 0, 0) : 1.f;
-      }
-#pragma unroll
-    for (int cb = 0; cb < CB; ++cb)
+    for (int cb = 0; cb < CB; ++cb) {
+      if (!part[cb]) continue;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int ml = wm * MI * 32 + rb * 16 + 4 * g + r;
-        float val = acc[rb][cb][r];
-        if (has_scale) val *= scale_s[ml];
-        val += bias_s[ml];
-        if (Rn) val += ext[cb][r];
-        if (epi.relu) val = fmaxf(val, 0.f);
-        if (Mn && !(msk[cb][r] > 0.f)) val = 0.f;
-        raw_buffer_store_f32(val, y_rsrc, off[cb][r], 0, 0);
+        int er, ec;
+        const bool in = ws_group_elem(prc[cb] >> 16, prc[cb] & 0xffff, r, TH, TW, it.h0, it.w0,
+                                      H, W, &er, &ec);
+        eo[cb][r] = (rowo | prc[cb]) >= 0 && in ? rowo + ((it.h0 + er) * W + it.w0 + ec) * 4 : kBufOOB;
+        e4[cb][r] = Rn ? raw_buffer_load_f32(r_rsrc, eo[cb][r], 0, 0) : 0.f;
+        m4[cb][r] = Mn ? raw_buffer_load_f32(m_rsrc, eo[cb][r], 0, 0) : 1.f;
       }
+    }
+#pragma unroll
+    for (int cb = 0; cb < CB; ++cb) {
+      f32x4 v;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) v[r] = finish(acc[rb][cb][r], sc, bi, ext[cb][r], msk[cb][r]);
+      raw_buffer_store_v4f32(v, y_rsrc, off[cb], 0, 0);
+    }
+#pragma unroll
+    for (int cb = 0; cb < CB; ++cb) {
+      if (!part[cb]) continue;
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        raw_buffer_store_f32(finish(acc[rb][cb][r], sc, bi, e4[cb][r], m4[cb][r]), y_rsrc,
+                             eo[cb][r], 0, 0);
+    }
   }
 }
 
@@ -2630,6 +2730,62 @@ extern "C" size_t tlod_conv_fwd_bs_workspace_bytes(int N, int Cin, int H, int W,
                            nullptr, 0, nullptr, &b) != kOk)
     return 0;
   return b;
+}
+
+// Host replay of conv_fwd_bs_ws_kernel's epilogue on one channel plane of an H x W map, with
+// the kernel's own classification (ws_group / ws_group_elem, or ws_pool_store for the pooling
+// form, which writes the (H / 2) x (W / 2) pooled map and nothing else) and address
+// arithmetic: a 16-B (8-B) store covers the four (two) floats from its first element's
+// address on, wherever they fall.
+extern "C" int tlod_conv_ws_store_map(int H, int W, int pool, int* wide, int* single, int* tile,
+                                      int* stray) {
+  TLOD_CHECK_ARG(H > 0 && W > 0 && (long long)H * W < (1ll << 29) && wide && single && stray,
+                 "bad map");
+  TLOD_CHECK_ARG(!pool || (H >= 2 && W >= 2), "pooling needs a 2 x 2 map");
+  const WsTile wt = ws_tile(H, W, pool != 0);
+  if (tile != nullptr) {
+    tile[0] = wt.th;
+    tile[1] = wt.tw;
+  }
+  const int Ho = pool ? H / 2 : H, Wo = pool ? W / 2 : W;  // the map the epilogue writes
+  std::fill(wide, wide + (size_t)Ho * Wo, 0);
+  std::fill(single, single + (size_t)Ho * Wo, 0);
+  int bad = 0;
+  // n floats from element `first` of map row `row`, as one store
+  auto put = [&](int* cnt, int row, long long first, int n) {
+    for (int e = 0; e < n; ++e) {
+      if (first + e >= (long long)Ho * Wo || (first + e) / Wo != row) ++bad;
+      else ++cnt[first + e];
+    }
+  };
+  for (int h0 = 0; h0 < H; h0 += wt.th)
+    for (int w0 = 0; w0 < W; w0 += wt.tw) {
+      if (pool) {  // (wn, hh, g): pixel rows 2 wn, 2 wn + 1, columns 16 hh + 4 g .. + 3
+        for (int wn = 0; wn < 8; ++wn)
+          for (int c = 0; c < 32; c += 4) {
+            const int hp = (h0 + 2 * wn) / 2, wp = (w0 + c) / 2;
+            const int pk = ws_pool_store(hp, wp, Ho, Wo);
+            if (pk == kWsPoolPair) put(wide, hp, (long long)hp * Wo + wp, 2);
+            else if (pk == kWsPoolOne) put(single, hp, (long long)hp * Wo + wp, 1);
+          }
+        continue;
+      }
+      for (int q0 = 0; q0 < 512; q0 += 4) {  // (wn, cb, g) of the eight MFMA waves' columns
+        const WsGroup gk = ws_group(q0, wt.th, wt.tw, h0, w0, H, W);
+        if (gk.kind == kWsRun) {
+          put(wide, h0 + gk.r, (long long)(h0 + gk.r) * W + w0 + gk.c, 4);
+        } else if (gk.kind == kWsPartial) {
+          for (int e = 0; e < 4; ++e) {
+            int er, ec;
+            if (!ws_group_elem(gk.r, gk.c, e, wt.th, wt.tw, h0, w0, H, W, &er, &ec)) continue;
+            if (h0 + er >= H || w0 + ec >= W) ++bad;
+            else ++single[(size_t)(h0 + er) * W + w0 + ec];
+          }
+        }
+      }
+    }
+  *stray = bad;
+  return kOk;
 }
 
 extern "C" int tlod_conv_fwd_bs_f32(const float* x, const void* wp, const float* scale,

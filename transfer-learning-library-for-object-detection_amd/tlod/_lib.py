@@ -274,6 +274,12 @@ SELFTRAIN_SIGNATURES = {
                                                 P, P]),
 }
 
+# include/tlod_plan.h: host-only queries of a kernel's plan (no GPU), a sixth table with its own
+# header (ledger: tests/test_wide_epilogue_cpu.py)
+PLAN_SIGNATURES = {
+    "tlod_conv_ws_store_map": (c_int, [c_int, c_int, c_int, P, P, P, P]),
+}
+
 _lib = None
 
 
@@ -289,7 +295,8 @@ def lib():
         for name, (res, args) in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items())
                                   + list(PA_ATF_SIGNATURES.items())
                                   + list(ROI_SIGNATURES.items())
-                                  + list(SELFTRAIN_SIGNATURES.items())):
+                                  + list(SELFTRAIN_SIGNATURES.items())
+                                  + list(PLAN_SIGNATURES.items())):
             if os.environ.get("TLOD_LIB") and not hasattr(L, name):
                 continue  # an older tuning build (A/B timing) may predate an entry point
             fn = getattr(L, name)
