@@ -62,10 +62,13 @@ int tlod_idf_sep_bwd_f32(const float* a, const float* b, const float* att_a, con
  *   z_ins (R, 2): the instance discriminator's logits; loss[n_img] = FocalLoss(class_num = 2,
  *     gamma)(z_ins, label_ins) = mean_r -(1 - P_r)^gamma log P_r, P_r =
  *     clamp(softmax(z_ins[r])[label_ins], 1e-6, 1) (net_utils.py:151-177).  R >= 1.
- *   Labels are 0 or 1.  loss holds n_img + 1 floats.
+ *   Labels are 0 or 1; gamma > 0 (anything else is refused: pow(1 - P, gamma) at P = 1 has no
+ *   finite meaning there).  loss holds n_img + 1 floats.
  * Backward from g_loss (n_img + 1), one upstream scalar per term: dz_img = g_loss[i] (softmax -
  *   onehot); dz_ins = g_loss[n_img] / R * dL/dP * dP/dz, 0 in rows where the fp32 softmax[label]
- *   is below 1e-6 (the clamp's gradient, as in the reference).  One launch each. */
+ *   is below 1e-6 (the clamp's gradient, as in the reference) and in rows where 1 - P is 0 in
+ *   double (the label's logit leads by about 37 or more), for every gamma > 0, gamma < 1
+ *   included.  One launch each. */
 int tlod_idf_domain_loss_f32(const float* z_img, int n_img, int label_img, const float* z_ins,
                              int R, int label_ins, float gamma, float* loss,
                              tlod_stream_t stream);

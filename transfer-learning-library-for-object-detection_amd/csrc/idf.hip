@@ -237,8 +237,10 @@ domain_loss_bwd_kernel(const float* __restrict__ z_img, int n_img, int label_img
   if (r >= R) return;
   const double p = p_label(z_ins + 2 * (size_t)r, label_ins);
   double g = 0.0;
-  if (!((float)p < 1e-6f)) {
-    const double q = 1.0 - p;
+  const double q = 1.0 - p;
+  // q == 0 (the label leads by 37 or more): the gradient is below 1e-16 of g_loss / R and the
+  // formula gives 0 for gamma >= 1; for gamma < 1 pow(0, gamma - 1) * log(1) would be inf * 0
+  if (!((float)p < 1e-6f) && (q > 0.0 || gamma >= 1.0)) {
     // L = -(1 - P)^gamma log P; dL/dP = gamma (1 - P)^(gamma - 1) log P - (1 - P)^gamma / P
     const double dLdP = gamma * pow(q, gamma - 1.0) * log(p) - pow(q, gamma) / p;
     g = (double)g_loss[n_img] / (double)R * dLdP * p * q;  // dP / dz[label] = P (1 - P)
@@ -348,6 +350,7 @@ int tlod_idf_domain_loss_f32(const float* z_img, int n_img, int label_img, const
   TLOD_CHECK_ARG(n_img >= 0 && R > 0, "bad shape");
   TLOD_CHECK_ARG((label_img == 0 || label_img == 1) && (label_ins == 0 || label_ins == 1),
                  "labels are 0 or 1");
+  TLOD_CHECK_ARG(gamma > 0.f, "gamma must be positive");
   domain_loss_fwd_kernel<<<1, kRed, 0, (hipStream_t)stream>>>(z_img, n_img, label_img, z_ins, R,
                                                               label_ins, (double)gamma, loss);
   TLOD_LAUNCH_CHECK();
@@ -362,6 +365,7 @@ int tlod_idf_domain_loss_bwd_f32(const float* z_img, int n_img, int label_img,
   TLOD_CHECK_ARG(n_img >= 0 && R > 0, "bad shape");
   TLOD_CHECK_ARG((label_img == 0 || label_img == 1) && (label_ins == 0 || label_ins == 1),
                  "labels are 0 or 1");
+  TLOD_CHECK_ARG(gamma > 0.f, "gamma must be positive");
   domain_loss_bwd_kernel<<<div_up(n_img + R, kRed), kRed, 0, (hipStream_t)stream>>>(
       z_img, n_img, label_img, z_ins, R, label_ins, (double)gamma, g_loss, dz_img, dz_ins);
   TLOD_LAUNCH_CHECK();
